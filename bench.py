@@ -4,7 +4,9 @@
 A "step" is one full window solve (Estimator::optimization()'s ceres::Solve replacement) of the
 BASELINE.json configs[1] workload -- 10 keyframes, 1k landmarks, 30k LiDAR edge/plane points -- with
 the factor tables and the state already resident in HBM; value = trust-region iterations executed /
-wall time (whole job, all ranks).  One JSON line on rank 0 (contract in the task statement), carrying
+wall time (whole job, all ranks).  One JSON line on rank 0 (contract in the task statement).  A plain run
+times --steps steps once and prints the headline (value, ms_per_step); --dump-outputs DIR also writes what
+the last timed step returned.  --full adds the measurements beside `value`, among them
   roofline     : the factor-sweep kernel (dominant kernel), HIP-event timed on the library's stream
   cpu_baseline : the CPU restatement of the reference algorithm (oracle/, kind "port"), single thread
                  like the reference's ceres::Solve (no num_threads set, estimator.cpp:1400-1411)
@@ -159,6 +161,23 @@ def cpu_baseline(w, opts, budget_s=10.0):
             "all_cores": {"value": mt_rate, "unit": "iterations/s", "cores": nthr,
                           "sample": "%d solves, factor sweep on %d threads = best of the team sizes 4/8/16/32 (Schur complement / Cholesky / dogleg stay serial)" % (mt_n, nthr)},
             "note": "CPU restatement of the reference algorithm (Ceres unavailable); %s; host has %d usable cores" % (build_note, ncpu)}
+
+
+def dump_outputs(d, be, w, summ):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the solved state (vil_download_state) and the summary
+    (iterations, successful steps, termination, initial / final cost, per-iteration cost and radius traces) -- as float64 DIR/<name>.npy.  The window
+    is seeded and the time cap is off, so two builds given the same arguments can be compared file for file.  w's own state stays the initial one."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    st0 = w.state_copy()
+    be.download_state(w)
+    out = w.state_copy()
+    w.set_state(st0)
+    n = min(summ.iterations, len(summ.cost_trace))
+    out["summary"] = [summ.iterations, summ.successful_steps, summ.termination, summ.initial_cost, summ.final_cost]
+    out["cost_trace"], out["radius_trace"] = summ.cost_trace[:n], summ.radius_trace[:n]
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 PHASE_NAMES = ["first workgroup started", "last visual / LiDAR / ICP-LPS role done", "last IMU role done", "chain workgroup saw the IMU / prior records", "chain: W^T complete", "last gather workgroup done",
@@ -728,7 +747,12 @@ def main():
     ap.add_argument("--force-comm", action="store_true", help="test hook: take the multi-GPU code path (process group, communicator, replicas leg) with a single rank")
     ap.add_argument("--replicas", action="store_true", help="N>1: independent replicas instead of sharding one window over RCCL")
     ap.add_argument("--ipc", action="store_true", help="N>1: the library's peer-buffer exchange (IPC-mapped inboxes over xGMI, vil_comm_ipc_*) instead of RCCL for the per-iteration collective")
+    ap.add_argument("--full", action="store_true", help="headline mode: everything beside `value` as well -- five timed regions (value = median), the HIP-event roofline pass, the two-launch "
+                    "structure, the PCIe-inclusive legs, the configs[2] / configs[3] windows, the CPU baseline, the replicas leg (N > 1).  Without it: ONE region of --steps steps")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", help="headline mode: write what the last timed step returned to its caller (solved state, summary) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.dump_outputs and (args.batch or args.scale_sweep or args.vgicp or args.mapreg or args.preint or args.replay):
+        ap.error("--dump-outputs writes the headline solve's outputs; the other modes have none to write")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher -- one rank per GPU under torch.distributed.run, rendezvous on 127.0.0.1
@@ -874,9 +898,9 @@ def main():
         return its, last_
 
     run(args.warmup)
-    # the timed region: EXACTLY args.steps steps between barrier + synchronise on both sides -- repeated REPEATS times back to back (an
-    # 18 ms region is noisy on a shared host): `value` / `ms_per_step` are the MEDIAN region, all regions are printed in `repeats`
-    REPEATS = 5
+    # the timed region: EXACTLY args.steps steps between barrier + synchronise on both sides.  --full repeats it REPEATS times back to back (an
+    # 18 ms region is noisy on a shared host): `value` / `ms_per_step` are then the MEDIAN region, all regions are printed in `repeats`
+    REPEATS = 5 if args.full else 1
     regions = []
     for _ in range(REPEATS):
         sync()
@@ -885,6 +909,8 @@ def main():
         sync()
         regions.append((time.perf_counter() - t0, iters))
     el, iters = sorted(regions)[len(regions) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, be, w, last)
     # roofline leg: the SAME K steps once more with HIP events recorded on the library's stream around every sweep
     # launch.  Kept out of the `value` region because three event records per ~170 us iteration perturb this
     # latency-bound pipeline by several percent.
@@ -893,7 +919,7 @@ def main():
     lpi0, one0 = C.c_int32(0), C.c_int32(0)
     be.lib.vil_debug_get_launch_structure(be.ctx, C.byref(lpi0), C.byref(one0))
     persistent = one0.value == 1 and lpi0.value == 0      # the whole solve is one resident launch (k_solve): events around THAT launch + its own stamps (profile mode 2 keeps the launch structure)
-    if not args.no_events:
+    if args.full and not args.no_events:
         be.lib.vil_profile_enable(be.ctx, 2 if persistent else 1)
         run(2)
         be.lib.vil_profile_read(be.ctx, C.byref(prof), 1)
@@ -911,7 +937,7 @@ def main():
     # the same window through the TWO-launch structure of round 4 (k_sweep, then gather + step): the sweep kernel in isolation -- its HIP-event average is what a
     # rocprofv3 --kernel-trace of that structure shows -- and the iteration rate the one-launch iteration is measured against.  Not `value`.
     two_launch = None
-    if one_launch and world == 1 and not args.no_events:
+    if args.full and one_launch and world == 1 and not args.no_events:
         be3 = lib.open_vilsolve(device=local)
         be3.lib.vil_debug_set_launch_mode(be3.ctx, 3)
         be3.upload(w)
@@ -958,7 +984,7 @@ def main():
     # N > 1, sharded: a second, clearly labelled leg with the SAME K steps run as N independent replicas (one whole window
     # per GPU, no collective) -- the throughput a multi-session deployment gets from the same hardware.  Not `value`.
     replicas_leg = None
-    if sharded and dist is not None:
+    if args.full and sharded and dist is not None:
         be2 = lib.open_vilsolve(device=local, rank=0, world=1)
         be2.upload(w)
         for _ in range(max(1, args.warmup)):
@@ -977,7 +1003,7 @@ def main():
     # what a tracker gets: a fresh upload per image (vil_solve = pack + H2D + set-up + solve + read-back), never a re-solve of a resident
     # upload -- reported beside `value`, never as `value`
     pcie_leg = None
-    if world == 1 and not args.no_tracker:
+    if args.full and world == 1 and not args.no_tracker:
         saved = w.state_copy()
         for _ in range(2):
             w.set_state(saved); be.solve(w, opts)
@@ -1024,7 +1050,7 @@ def main():
                "workload": "BASELINE.json configs[%d]: K=%d, L=%d, %d visual factors, %d LiDAR points, prior n=%d, %s" % (cfg_id - 1, wx.K, wx.L, len(wx.vis_i), len(wx.plane_pose) + len(wx.edge_pose), wx.prior.n, "sharded over %d GPUs" % world if sharded else ("1 GPU" if world == 1 else "%d replicas" % world))}
         return leg, wx, profx, nx
     cfg3_leg = cfg4_leg = None
-    if args.config == 2 and not args.no_cfg3:
+    if args.full and args.config == 2 and not args.no_cfg3:
         cfg3_leg, w3, prof3, n3 = window_leg(3)
         cfg4_leg, w4, prof4, n4 = window_leg(4)
     if rank == 0:
@@ -1033,14 +1059,15 @@ def main():
             "value": tot_iters / max_el, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * max_el / args.steps, "higher_is_better": True, "scaling": ("strong" if sharded else "weak"), "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
-            "repeats": {"regions": len(region_vals), "steps_per_region": args.steps, "value_is": "median region", "median": float(sorted(region_vals)[len(region_vals) // 2]),
-                        "min": float(min(region_vals)), "max": float(max(region_vals)), "all": [float(v) for v in region_vals]},
             "config": {"workload": "BASELINE.json configs[%d]: K=%d keyframes, L=%d landmarks, %d visual factors, %d plane + %d edge LiDAR points, %d IMU, %d ICP, %d LPS, prior n=%d (%s)"
                        % (args.config - 1, w.K, w.L, len(w.vis_i), len(w.plane_pose), len(w.edge_pose), len(w.imu_i), len(w.icp_ids), len(w.lps_ids), w.prior.n, prior_kind),
                        "iterations_per_solve": last.iterations, "termination": abi.TERM_NAMES[last.termination], "final_cost": last.final_cost,
                        "parallelism": "1 GPU" if world == 1 else (("factor set of ONE window sharded over %d GPUs: visual by landmark owner, LiDAR points in contiguous slices, ONE " % world) + ("peer-buffer exchange (IPC inboxes over xGMI)" if args.ipc else "RCCL all-reduce") + " per iteration of the whole linear-system set ([S|g|cost] + the owners' landmark arrays), then the complete step kernel redundantly on every rank; NO N > 1 curve of this code had been measured on hardware before this run (one GPU per build box)" if sharded else "%d independent replicas" % world),
                        "step": "one full window solve, inputs resident in HBM"},
         }
+        if args.full:
+            out["repeats"] = {"regions": len(region_vals), "steps_per_region": args.steps, "value_is": "median region", "median": float(sorted(region_vals)[len(region_vals) // 2]),
+                              "min": float(min(region_vals)), "max": float(max(region_vals)), "all": [float(v) for v in region_vals]}
         if shard_note:
             out["config"]["note"] = shard_note
         if replicas_leg:
@@ -1083,7 +1110,7 @@ def main():
                 cfg4_leg["roofline"] = roofline_obj(w4, prof4, "a further pass of the same %d steps with HIP events enabled" % n4, ("r06_pmc_fetch_size_c4.csv", "r06_pmc_write_size_c4.csv"),
                                                     "profiles/r06_pmc_{fetch,write}_size_c4.csv (rocprofv3 --pmc passes of bench.py --config 4)", "r06_pmc_mfma_c4.csv", one_launch=leg_one.get(4, False), phases=leg_phases.get(4))
             out["configs3_window"] = cfg4_leg
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(w, opts)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_all_cores"] = out["value"] / out["cpu_baseline"]["all_cores"]["value"]

@@ -21,7 +21,7 @@ def _line(out):
 
 def test_bench_gpus_2_spawns_two_ranks_that_share_one_window():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ipc", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-cfg3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ipc", "--full", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-cfg3"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     r = _line(out)
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["steps"] == 4, r

@@ -1,6 +1,6 @@
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd /tmp
-timeout 300 python $R/bench.py --steps 40 --warmup 5 > $O/r01_bench.json 2>/dev/null
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --steps 40 --warmup 5 --no-cpu > /dev/null 2>&1
+timeout 300 python $R/bench.py --full --steps 40 --warmup 5 > $O/r01_bench.json 2>/dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --full --steps 40 --warmup 5 --no-cpu > /dev/null 2>&1
 find /tmp/p_trace -name "*kernel_stats.csv" -exec cp {} $O/r01_kernel_stats.csv \;
 find /tmp/p_trace -name "*kernel_trace.csv" -exec cp {} $O/r01_kernel_trace.csv \;
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- python $R/bench.py --steps 10 --warmup 2 --no-cpu --no-events > /dev/null 2>&1

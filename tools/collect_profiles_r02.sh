@@ -1,10 +1,10 @@
 # Round-2 evidence (one gpurun call): bench line, rocprofv3 --kernel-trace --stats of the same command for configs[1], [2], [3],
 # separate --pmc passes (FETCH_SIZE / WRITE_SIZE / MFMA counters) of the configs[1] command, replay, full-size config table.
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd /tmp
-timeout 300 python $R/bench.py --steps 40 --warmup 5 > $O/r02_bench.json 2>/dev/null
+timeout 300 python $R/bench.py --full --steps 40 --warmup 5 > $O/r02_bench.json 2>/dev/null
 for cfg in 2 3 4; do
   rm -rf /tmp/p_trace
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --config $cfg --steps 20 --warmup 3 --no-cpu --no-cfg3 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu --no-cfg3 > /dev/null 2>&1
   sfx=""; [ $cfg != 2 ] && sfx="_c$cfg"
   find /tmp/p_trace -name "*kernel_stats.csv" -exec cp {} $O/r02_kernel_stats$sfx.csv \;
   find /tmp/p_trace -name "*kernel_trace.csv" -exec cp {} $O/r02_kernel_trace$sfx.csv \;

@@ -4,7 +4,7 @@ export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04; mkdir -p $O; cd /tm
 for cfg in 2 3 4; do
   sfx=""; [ $cfg != 2 ] && sfx="_c$cfg"
   rm -rf /tmp/p_trace
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --config $cfg --steps 20 --warmup 3 --no-cpu --no-cfg3 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu --no-cfg3 > /dev/null 2>&1
   find /tmp/p_trace -name "*kernel_stats.csv" -exec cp {} $O/r04_kernel_stats$sfx.csv \;
   find /tmp/p_trace -name "*kernel_trace.csv" -exec cp {} $O/r04_kernel_trace$sfx.csv \;
   for ctr in FETCH_SIZE WRITE_SIZE; do
@@ -38,5 +38,5 @@ fi
 timeout 900 python tools/run_configs.py > $O/r04_configs.txt 2>&1
 # the bench line LAST: it reads the --pmc CSVs of this very collection from profiles/ (copied there for the run)
 cp $O/r04_pmc_*.csv $R/profiles/ 2>/dev/null
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/r04_bench.json 2>$O/r04_bench.err
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/r04_bench.json 2>$O/r04_bench.err
 ls -la $O | tail -50; cat $O/r04_summary_c4.txt; cat $O/r04_configs.txt
