@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <array>
+#include <map>
 #include <memory>
 #include <pthread.h>
 
@@ -247,6 +248,14 @@ __global__ void k_slim_emul(double* Msum, double* Gall, PeerPtrs pp, SlimLay Y) 
 #define VIL_MAX_CHUNK 24       // iterations enqueued without a host round trip (the first solve of an upload: vil_solve_resident); vil_profile_enable sizes its events for it
 #define VIL_CHC_MAX 16384      // entries of the chain workgroup's gather table (K = 20: ~7000)
 #define VIL_SFLAG_MAX 4096      // sweep workgroups a one-launch iteration may have (configs[2]: ~600)
+// The launch structure of an uploaded window, decided once per upload (choose_structure): every launch of a solve and the solve's ladder read it
+struct Structure {
+    int chain = 0, chain_rs = 0, prechain = 0, rs_merged = 0, n_ww = 0, n_gather = 0, n_sw = 0;      // what DevP carries of it (vil_dev.hpp)
+    bool fused = false, persist = false;          // one launch per iteration (k_iter) / the whole solve in one resident launch (k_solve)
+    const void* sweep_fn = nullptr; const void* step_fn = nullptr; const void* iter_fn = nullptr;      // k_sweep<2 | 5>, the k_step variant, k_iter<2 | 5>: granted and launched
+    size_t lds_sweep = 0, lds_step = 0, lds_iter = 0, lds_solve = 0;
+    int n_sweep = 0, n_reduce = 0, n_reduce_po = 0, n_gather_m = 0, cap_fused = -1;       // workgroups: sweep roles, k_reduce (all / pose-only gather), gather of the merged launch; cap_fused: of k_iter, at lds_iter, the device holds at once (vil_solve_batch)
+};
 struct vil_ctx {
     int device = 0, rank = 0, world = 1;
     hipStream_t stream = nullptr;
@@ -267,21 +276,17 @@ struct vil_ctx {
     int64_t n_recovered = 0, n_aborted = 0;    // solves whose one-launch attempt gave up and were re-run with two launches per iteration / that failed on both
     bool reset_pending = false;       // vil_reset_state called, the copy not launched yet
     std::vector<int> plane_perm, edge_perm;   // sorted index -> caller index
-    int n_blocks_sweep = 0, n_blocks_reduce = 0, n_blocks_reduce_po = 0, n_gather_m = 0, n_ww = 0;      // n_ww: tiles of W W^T formed by extra workgroups of k_reduce (vil_prechain.hpp)
-    size_t lds_sweep = 0, lds_step = 0, lds_reduce = 0;
-    bool persist = false; size_t lds_solve = 0; int cap_solve[2] = {-1, -1}; size_t cap_solve_lds[2] = {0, 0}; int attr_solve[2] = {0, 0};      // the whole solve in one resident launch (k_solve<2 | 5>, vil_iter.hpp)
-    bool fused = false; size_t lds_iter = 0; int cap_iter[2] = {-1, -1}; size_t cap_iter_lds[2] = {0, 0}; int attr_iter[2] = {0, 0};      // the one-launch iteration (k_iter<2 | 5>, vil_iter.hpp)
-    int cap_step3 = -1; size_t cap_step3_lds = 0;      // workgroups of the merged gather + step launch the device holds at once AT THAT dynamic-LDS size (vil_coop.hpp)
+    Structure ls;                  // the launch structure of the uploaded window (choose_structure)
+    std::map<const void*, int> lds_granted;      // per kernel: the largest dynamic-LDS size granted so far (grant_lds)
+    std::map<const void*, std::pair<size_t, int>> coop_caps;      // per kernel: (dynamic-LDS size probed last, workgroups the device holds at once AT that size) -- coop_capacity
     int vis_gm = 0;                      // doubles of operand rows the largest visual chunk of the uploaded window needs (vil_sweep.hpp)
     size_t span = 0;               // doubles of one linear-system set (SysBuf::ar): the multi-GPU all-reduce message
-    bool step_lds = false;
     int* d_status = nullptr;
     Ctl* h_ctl = nullptr;          // pinned
     int* h_word = nullptr;         // pinned: status words read back from the device
     char* h_mirror = nullptr; Ctl* d_hctl = nullptr; int* d_hseq = nullptr; double* d_hstate = nullptr; size_t mirror_ns = 0;      // pinned + mapped: Ctl | sequence word | final state, written by solve_finish (vil_finish.hpp)
     bool no_poll = false;          // VIL_NO_POLL=1: copy + synchronise instead of polling the mirror
     bool mirror_state = false;     // the mirror holds the final state of the last solve (vil_download_state needs no device operation)
-    int attr_sweep[2] = {0, 0}, attr_step[5] = {0, 0, 0, 0, 0}, attr_marg[2] = {0, 0}, attr_commit = 0;      // dynamic-LDS sizes already granted to the kernels (hipFuncSetAttribute is not free)
     double* h_pin = nullptr;       // pinned scratch
     char* marg_ws = nullptr;       // device work space of vil_marginalize (grow-only)
     unsigned long long* d_marg_ts = nullptr;      // phase stamps of the last marginalisation's kernels (vil_debug_marg_stamps)
@@ -389,6 +394,19 @@ static size_t step_static_lds(const void* fn) {
     if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return (size_t)64 * 1024; }
     known.emplace_back(fn, (size_t)fa.sharedSizeBytes);
     return (size_t)fa.sharedSizeBytes;
+}
+// hipFuncSetAttribute is not free: a kernel's dynamic-LDS limit is raised only when it needs more than it was granted before
+static hipError_t grant_lds(vil_ctx* c, const void* fn, size_t bytes) {
+    int& granted = c->lds_granted[fn];
+    const hipError_t e = (int)bytes > granted ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+    if (e == hipSuccess) granted = std::max(granted, (int)bytes);
+    return e;
+}
+// workgroups of a kernel the device holds at once AT THAT dynamic-LDS size (vil_coop.hpp): probed again when the size changes (42 kB at K = 10: 3 per CU, 95 kB at K = 20: 1)
+static int coop_capacity(vil_ctx* c, const void* fn, size_t lds) {
+    auto it = c->coop_caps.find(fn);
+    if (it == c->coop_caps.end() || it->second.first != lds) it = c->coop_caps.insert_or_assign(fn, std::make_pair(lds, vilcoop::capacity(fn, VIL_STEP_THREADS, lds, c->device))).first;
+    return it->second.second;
 }
 static SolveOpts to_dev_opts(const vil_options* o) {
     SolveOpts s;
@@ -682,11 +700,17 @@ static void landmark_frames(const vil_problem* p, std::vector<int>& lms, std::ve
     }
 }
 // helper workgroups of the step kernel for L landmarks: none below one landmark per master thread, else one per 128 (quad of lanes per landmark) or 256 (pair) landmarks, at most 15
-static int vil_helpers_for(int L) {
+// (a helper keeps its landmarks' rows in registers between its two passes while it has at least one thread per landmark -- vil_step.hpp, lm_rows_quad:
+//  up to 1920 landmarks a QUAD of threads per landmark, 128 landmarks per helper; beyond that a PAIR, 256 per helper; at most 15 helpers, so past
+//  3840 landmarks a helper's threads loop over its slice)
+// Master and helpers wait for one another inside the launch: all of them must be resident at once (vil_coop.hpp).  With its dynamic LDS a step workgroup
+// owns a compute unit; a device with fewer units than 1 + n_help runs without helpers.
+static int vil_helpers_for(int L, int device) {
     const int quad = VIL_STEP_THREADS / 4, pair = VIL_STEP_THREADS / 2;
-    if (L < VIL_STEP_THREADS) return 0;
-    if (L <= 15 * quad) return std::min(15, (L + quad - 1) / quad);
-    return std::min(15, (L + pair - 1) / pair);
+    int n = L < VIL_STEP_THREADS ? 0 : std::min(15, L <= 15 * quad ? (L + quad - 1) / quad : (L + pair - 1) / pair);
+    if (const char* ev = VIL_TUNE_ENV("VIL_HELP")) n = std::max(0, std::min(15, atoi(ev)));
+    if (1 + n > vilcoop::compute_units(device) / 2) n = 0;      // (what this process really has: a CU mask is not in the device attribute)
+    return n;
 }
 // Co-residency is decided per XCD: the dispatcher deals the workgroups of a grid round-robin to the eight XCDs, each of which places ITS share on ITS compute units.
 // n consecutive workgroups that wait for others therefore need ceil(n / 8) slots on every XCD, and one more for the workgroups they wait for to run through
@@ -741,219 +765,172 @@ static int shard_cut(const std::vector<int>& lms, int L, int r, int world) {
     return std::min((int)(std::lower_bound(lms.begin(), lms.end(), (int)target) - lms.begin()), L);
 }
 
-// check_setup: wait for k_setup's verdict (an IMU covariance that is not positive definite) and return it; false: nothing is waited for --
-// the first step kernel of the solve ends it with that status (DevP::setup_stat), and the launches of the solve queue up behind the upload
-static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, bool sharded, const vil_device_lidar* dl = nullptr, const vil_problem* gp = nullptr, int vis_f0 = 0, bool check_setup = true, const WinSrc* ws = nullptr) {
-    if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    int st = validate(p, s, dl != nullptr, ws != nullptr);
-    if (st != VIL_OK) return st;                 // an invalid problem leaves the resident one untouched
-    c->uploaded = false;                         // from here on the arena is rewritten: resident only again after a complete upload
-    c->resident_kind = 0; c->reset_pending = false;
-    HIPCHK(hipSetDevice(c->device));
-    const int K = p->K, L = p->L, D = 15 * K + 7, NV = 6 * K + 7, NS = 16 * K + 8 + L;
-#ifdef VIL_TUNING
-    static const bool up_trace = getenv("VIL_UPLOAD_TRACE") != nullptr;
-    auto up_t0 = std::chrono::steady_clock::now();
-    #define UPTICK(name) do { if (up_trace) { const auto t_ = std::chrono::steady_clock::now(); fprintf(stderr, "[upload] %-10s %7.1f us\n", name, std::chrono::duration<double, std::micro>(t_ - up_t0).count()); up_t0 = t_; } } while (0)
-#else
-    #define UPTICK(name) do {} while (0)
-#endif
-    Arena& ar = c->ar;
-    if (c->up_pending) { HIPCHK(hipEventSynchronize(c->up_ev)); c->up_pending = false; }
-    ar.reset();
-    DevP P; memset(&P, 0, sizeof P);
-    P.K = K; P.L = L; P.D = D; P.NV = NV; P.NS = NS;
-    P.ex_const = p->ex_const; P.use_td = p->use_td; P.td_free = (p->use_td && !p->td_const) ? 1 : 0;
-    memcpy(P.G, p->G, sizeof P.G); P.sqrt_info = p->sqrt_info_px; P.k_tr = p->tr_over_row;
-    { double R[9]; quat_to_R_host(p->q_lb, R); for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.Rbl[3 * i + j] = R[3 * j + i]; }
-      for (int i = 0; i < 3; ++i) P.tbl[i] = -(P.Rbl[3 * i] * p->t_lb[0] + P.Rbl[3 * i + 1] * p->t_lb[1] + P.Rbl[3 * i + 2] * p->t_lb[2]); }
+// ---- upload_impl, stage by stage.  Every table goes into ONE pinned image in the order of its put(): the arena layout is that order.
+struct ImageBuilder {
+    Arena& ar;
     struct Fix { size_t off; void** slot; bool scratch; };
-    std::vector<Fix> fix;
+    std::vector<Fix> fix;          // slots patched with the device address once the arena is allocated (commit)
     bool oom = false;
     // src != null: a table (copied into the pinned image); src == null: zero-initialised device work space
-    auto put = [&](const void* src, size_t bytes, void** slot) {
-        if (!src || !bytes) { const size_t o = ar.take_scratch(bytes ? bytes : 8); fix.push_back({o, slot, true}); return o; }
-        const size_t o = ar.take(bytes);
-        if (o == (size_t)-1) { oom = true; return (size_t)0; }
-        memcpy(ar.h + o, src, bytes); fix.push_back({o, slot, false});
-        return o;
-    };
+    void put(const void* src, size_t bytes, void** slot) {
+        if (!src || !bytes) fix.push_back({ar.take_scratch(bytes ? bytes : 8), slot, true});
+        else if (char* h = reserve(bytes, slot)) memcpy(h, src, bytes);
+    }
     // a table that is produced in place (transpositions): space in the pinned image, to be filled before the next put()
-    auto reserve = [&](size_t bytes, void** slot) -> char* {
+    char* reserve(size_t bytes, void** slot) {
         const size_t o = ar.take(bytes ? bytes : 8);
         if (o == (size_t)-1) { oom = true; return nullptr; }
         fix.push_back({o, slot, false});
         return ar.h + o;
-    };
-    // constancy
-    if (p->pose_const) put(p->pose_const, K, (void**)&P.pose_const);
-    if (p->sb_const) put(p->sb_const, K, (void**)&P.sb_const);
-    if (p->lm_const && L) put(p->lm_const, L, (void**)&P.lm_const);
-    // state x[0], x[1], backup
+    }
+};
+// the parameter block's header, constancy, state x[0], x[1] and its backups
+static void upload_state(vil_ctx* c, ImageBuilder& im, const vil_problem* p, const vil_state* s, const WinSrc* ws, DevP& P) {
+    const int K = p->K, L = p->L, NS = 16 * K + 8 + L;
+    P.K = K; P.L = L; P.D = 15 * K + 7; P.NV = 6 * K + 7; P.NS = NS;
+    P.ex_const = p->ex_const; P.use_td = p->use_td; P.td_free = (p->use_td && !p->td_const) ? 1 : 0;
+    memcpy(P.G, p->G, sizeof P.G); P.sqrt_info = p->sqrt_info_px; P.k_tr = p->tr_over_row;
+    { double R[9]; quat_to_R_host(p->q_lb, R); for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.Rbl[3 * i + j] = R[3 * j + i]; }
+      for (int i = 0; i < 3; ++i) P.tbl[i] = -(P.Rbl[3 * i] * p->t_lb[0] + P.Rbl[3 * i + 1] * p->t_lb[1] + P.Rbl[3 * i + 2] * p->t_lb[2]); }
+    if (p->pose_const) im.put(p->pose_const, K, (void**)&P.pose_const);
+    if (p->sb_const) im.put(p->sb_const, K, (void**)&P.sb_const);
+    if (p->lm_const && L) im.put(p->lm_const, L, (void**)&P.lm_const);
     std::vector<double> x(NS);
     memcpy(&x[0], s->pose, sizeof(double) * 7 * K); memcpy(&x[7 * K], s->speedbias, sizeof(double) * 9 * K);
     memcpy(&x[16 * K], s->ex_pose, sizeof(double) * 7); x[16 * K + 7] = s->td[0];
     if (L) memcpy(&x[16 * K + 8], s->inv_depth, sizeof(double) * L);
-    put(x.data(), sizeof(double) * NS, (void**)&P.x[0]);
-    if (ws) { put(nullptr, sizeof(double) * NS, (void**)&P.x[1]); put(nullptr, sizeof(double) * NS, (void**)&c->d_x0); }      // (k_win_pack copies them on the device)
-    else { put(x.data(), sizeof(double) * NS, (void**)&P.x[1]); put(x.data(), sizeof(double) * NS, (void**)&c->d_x0); }
-    put(nullptr, sizeof(double) * NS, (void**)&c->d_xsave);
-    UPTICK("head");
-    // visual
-    const int n_vis = ws ? ws->n_vis : p->n_vis;
+    im.put(x.data(), sizeof(double) * NS, (void**)&P.x[0]);
+    if (ws) { im.put(nullptr, sizeof(double) * NS, (void**)&P.x[1]); im.put(nullptr, sizeof(double) * NS, (void**)&c->d_x0); }      // (k_win_pack copies them on the device)
+    else { im.put(x.data(), sizeof(double) * NS, (void**)&P.x[1]); im.put(x.data(), sizeof(double) * NS, (void**)&c->d_x0); }
+    im.put(nullptr, sizeof(double) * NS, (void**)&c->d_xsave);
+}
+// visual tables, sorted and cut into chunks by plan_visual; wd_track / wd_startf: device copies of the landmark table (resident window)
+static int upload_visual(vil_ctx* c, ImageBuilder& im, const vil_problem* p, const WinSrc* ws, const vil_problem* gp, int vis_f0, DevP& P, int** wd_track, int** wd_startf) {
+    const int K = p->K, L = p->L, n_vis = ws ? ws->n_vis : p->n_vis;
     P.n_vis = n_vis; P.vis_stride = (n_vis + 31) & ~31;
-    int* wd_track = nullptr; int* wd_startf = nullptr;       // device copies of the landmark table (resident window)
-    {
-        std::vector<int> lms(L + 1, 0);
-        const int ws_lb = (ws && gp) ? ws->lb : 0, ws_le = (ws && gp) ? ws->le : L;      // resident window under a communicator: the factors of the owned landmarks only
-        if (ws) for (int l = 0; l < L; ++l) lms[l + 1] = lms[l] + ((l >= ws_lb && l < ws_le) ? ws->lm_nobs[l] - 1 : 0);
-        else {
-            for (int f = 0; f < p->n_vis; ++f) lms[p->vis_l[f] + 1]++;
-            for (int l = 0; l < L; ++l) lms[l + 1] += lms[l];
+    // factor prefix, frame window and anchor of every landmark, then the plan of the visual role (plan_visual above: sorted order, chunks, device tables)
+    std::vector<int> lms, fmin, fmax, anch;
+    if (ws) {
+        const int ws_lb = gp ? ws->lb : 0, ws_le = gp ? ws->le : L;      // resident window under a communicator: the factors of the owned landmarks only
+        lms.assign(L + 1, 0); fmin.assign(std::max(L, 1), K); fmax.assign(std::max(L, 1), -1); anch.assign(std::max(L, 1), 0);
+        for (int l = 0; l < L; ++l) lms[l + 1] = lms[l] + ((l >= ws_lb && l < ws_le) ? ws->lm_nobs[l] - 1 : 0);
+        for (int l = ws_lb; l < ws_le; ++l) { anch[l] = fmin[l] = ws->lm_startf[l]; fmax[l] = ws->lm_startf[l] + ws->lm_nobs[l] - 1; }
+    } else landmark_frames(p, lms, fmin, fmax, anch);
+    VisPlan vp;
+    int npt = std::max(p->n_plane, 0), net = std::max(p->n_edge, 0);           // LiDAR points of this upload (resident slabs: what they hold)
+    if (p->n_plane == VIL_LIDAR_RESIDENT) for (auto& sl : c->slabs) { npt += sl.np; net += sl.ne; }
+    int vwg_max = visual_wg_budget(p->n_imu, npt, net), cap_forced = 0;
+    if (const char* ev = VIL_TUNE_ENV("VIL_VWG")) vwg_max = std::max(1, atoi(ev));
+    if (const char* ev = VIL_TUNE_ENV("VIL_VCAP")) cap_forced = std::max(1, atoi(ev));
+    if (!plan_visual(K, L, n_vis, lms, fmin, fmax, anch, vwg_max, cap_forced, vp)) return VIL_ERR_UNSUPPORTED;
+    const std::vector<int>& fperm = vp.fperm; const std::vector<int>& finv = vp.finv;
+    im.put(finv.data(), 4 * finv.size(), (void**)&P.vfinv);
+    if (ws) {
+        // resident window: the factor tables are device work space, k_win_pack fills them from the observation store
+        im.put(nullptr, 8 * (size_t)14 * std::max(P.vis_stride, 1), (void**)&P.vis_c);
+        im.put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_i); im.put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_j); im.put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_l);
+        im.put(ws->lm_track, 4 * (size_t)std::max(L, 1), (void**)wd_track); im.put(ws->lm_startf, 4 * (size_t)std::max(L, 1), (void**)wd_startf);
+    } else {
+        if (double* soa = (double*)im.reserve(8 * (size_t)14 * std::max(P.vis_stride, 1), (void**)&P.vis_c)) {
+            for (int q = 0; q < 14; ++q) {
+                double* row = soa + (size_t)q * P.vis_stride;
+                for (int pos = 0; pos < p->n_vis; ++pos) row[pos] = p->vis_const[(size_t)fperm[pos] * 14 + q];
+                for (int f = p->n_vis; f < P.vis_stride; ++f) row[f] = 0.0;
+            }
         }
-        // frame window of every landmark, then the plan of the visual role (plan_visual above: sorted order, chunks, device tables)
-        std::vector<int> fmin(std::max(L, 1), K), fmax(std::max(L, 1), -1), anch(std::max(L, 1), 0);
-        if (ws) { for (int l = ws_lb; l < ws_le; ++l) { anch[l] = fmin[l] = ws->lm_startf[l]; fmax[l] = ws->lm_startf[l] + ws->lm_nobs[l] - 1; } }
-        else for (int f = 0; f < p->n_vis; ++f) {
-            const int l = p->vis_l[f], lo = std::min(p->vis_i[f], p->vis_j[f]), hi = std::max(p->vis_i[f], p->vis_j[f]);
-            anch[l] = p->vis_i[f]; fmin[l] = std::min(fmin[l], lo); fmax[l] = std::max(fmax[l], hi);
-        }
-        VisPlan vp;
-        {
-            int npt = std::max(p->n_plane, 0), net = std::max(p->n_edge, 0);           // LiDAR points of this upload (resident slabs: what they hold)
-            if (p->n_plane == VIL_LIDAR_RESIDENT) for (auto& sl : c->slabs) { npt += sl.np; net += sl.ne; }
-            int vwg_max = visual_wg_budget(p->n_imu, npt, net), cap_forced = 0;
-            if (const char* ev = VIL_TUNE_ENV("VIL_VWG")) vwg_max = std::max(1, atoi(ev));
-            if (const char* ev = VIL_TUNE_ENV("VIL_VCAP")) cap_forced = std::max(1, atoi(ev));
-            if (!plan_visual(K, L, n_vis, lms, fmin, fmax, anch, vwg_max, cap_forced, vp)) return VIL_ERR_UNSUPPORTED;
-        }
-        const std::vector<int>& fperm = vp.fperm; const std::vector<int>& finv = vp.finv;
-        put(finv.data(), 4 * finv.size(), (void**)&P.vfinv);
+        std::vector<int> si(std::max(p->n_vis, 1)), sj(std::max(p->n_vis, 1)), sl(std::max(p->n_vis, 1));
+        for (int pos = 0; pos < p->n_vis; ++pos) { si[pos] = p->vis_i[fperm[pos]]; sj[pos] = p->vis_j[fperm[pos]]; sl[pos] = p->vis_l[fperm[pos]]; }
+        im.put(si.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_i); im.put(sj.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_j); im.put(sl.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_l);
+    }
+    im.put(lms.data(), 4 * (size_t)(L + 1), (void**)&P.lm_start);
+    std::vector<int> acol(std::max(L, 1), -1);
+    if (ws) {
+        for (int l = 0; l < L; ++l) acol[l] = 6 * ws->lm_startf[l];
+        im.put(acol.data(), 4 * acol.size(), (void**)&P.lm_acol); im.put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.fcol);
+    } else {
+        std::vector<int> fcol(std::max(p->n_vis, 1), 0);
+        for (int f = p->n_vis - 1; f >= 0; --f) { acol[p->vis_l[f]] = 6 * p->vis_i[f]; fcol[f] = 6 * p->vis_j[f]; }
+        im.put(acol.data(), 4 * acol.size(), (void**)&P.lm_acol); im.put(fcol.data(), 4 * fcol.size(), (void**)&P.fcol);
+    }
+    if (gp) {                                        // tables of the whole window for the step kernel (every rank walks every landmark)
+        const int gnv = ws ? ws->n_vis_all : gp->n_vis;
+        std::vector<int> gl(L + 1, 0), gac(std::max(L, 1), -1), gfc(std::max(gnv, 1), 0);
         if (ws) {
-            // resident window: the factor tables are device work space, k_win_pack fills them from the observation store
-            put(nullptr, 8 * (size_t)14 * std::max(P.vis_stride, 1), (void**)&P.vis_c);
-            put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_i); put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_j); put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.vis_l);
-            put(ws->lm_track, 4 * (size_t)std::max(L, 1), (void**)&wd_track); put(ws->lm_startf, 4 * (size_t)std::max(L, 1), (void**)&wd_startf);
+            for (int l = 0; l < L; ++l) {
+                gl[l + 1] = gl[l] + ws->lm_nobs[l] - 1; gac[l] = 6 * ws->lm_startf[l];
+                for (int q = 1; q < ws->lm_nobs[l]; ++q) gfc[gl[l] + q - 1] = 6 * (ws->lm_startf[l] + q);
+            }
         } else {
-            if (double* soa = (double*)reserve(8 * (size_t)14 * std::max(P.vis_stride, 1), (void**)&P.vis_c)) {
-                for (int q = 0; q < 14; ++q) {
-                    double* row = soa + (size_t)q * P.vis_stride;
-                    for (int pos = 0; pos < p->n_vis; ++pos) row[pos] = p->vis_const[(size_t)fperm[pos] * 14 + q];
-                    for (int f = p->n_vis; f < P.vis_stride; ++f) row[f] = 0.0;
-                }
-            }
-            std::vector<int> si(std::max(p->n_vis, 1)), sj(std::max(p->n_vis, 1)), sl(std::max(p->n_vis, 1));
-            for (int pos = 0; pos < p->n_vis; ++pos) { si[pos] = p->vis_i[fperm[pos]]; sj[pos] = p->vis_j[fperm[pos]]; sl[pos] = p->vis_l[fperm[pos]]; }
-            put(si.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_i); put(sj.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_j); put(sl.data(), 4 * (size_t)p->n_vis, (void**)&P.vis_l);
+            for (int f = 0; f < gp->n_vis; ++f) gl[gp->vis_l[f] + 1]++;
+            for (int l = 0; l < L; ++l) gl[l + 1] += gl[l];
+            for (int f = gp->n_vis - 1; f >= 0; --f) { gac[gp->vis_l[f]] = 6 * gp->vis_i[f]; gfc[f] = 6 * gp->vis_j[f]; }
         }
-        put(lms.data(), 4 * (size_t)(L + 1), (void**)&P.lm_start);
-        {
-            std::vector<int> acol(std::max(L, 1), -1);
-            if (ws) {
-                for (int l = 0; l < L; ++l) acol[l] = 6 * ws->lm_startf[l];
-                put(acol.data(), 4 * acol.size(), (void**)&P.lm_acol); put(nullptr, 4 * (size_t)std::max(n_vis, 1), (void**)&P.fcol);
-            } else {
-                std::vector<int> fcol(std::max(p->n_vis, 1), 0);
-                for (int f = p->n_vis - 1; f >= 0; --f) { acol[p->vis_l[f]] = 6 * p->vis_i[f]; fcol[f] = 6 * p->vis_j[f]; }
-                put(acol.data(), 4 * acol.size(), (void**)&P.lm_acol); put(fcol.data(), 4 * fcol.size(), (void**)&P.fcol);
-            }
-        }
-        P.vis_f0 = 0;
-        if (gp) {                                        // tables of the whole window for the step kernel (every rank walks every landmark)
-            const int gnv = ws ? ws->n_vis_all : gp->n_vis;
-            std::vector<int> gl(L + 1, 0), gac(std::max(L, 1), -1), gfc(std::max(gnv, 1), 0);
-            if (ws) {
-                for (int l = 0; l < L; ++l) {
-                    gl[l + 1] = gl[l] + ws->lm_nobs[l] - 1; gac[l] = 6 * ws->lm_startf[l];
-                    for (int q = 1; q < ws->lm_nobs[l]; ++q) gfc[gl[l] + q - 1] = 6 * (ws->lm_startf[l] + q);
-                }
-            } else {
-                for (int f = 0; f < gp->n_vis; ++f) gl[gp->vis_l[f] + 1]++;
-                for (int l = 0; l < L; ++l) gl[l + 1] += gl[l];
-                for (int f = gp->n_vis - 1; f >= 0; --f) { gac[gp->vis_l[f]] = 6 * gp->vis_i[f]; gfc[f] = 6 * gp->vis_j[f]; }
-            }
-            put(gl.data(), 4 * gl.size(), (void**)&P.glm_start); put(gac.data(), 4 * gac.size(), (void**)&P.glm_acol); put(gfc.data(), 4 * gfc.size(), (void**)&P.gfcol);
-            P.vis_f0 = vis_f0;
-        }
-        P.n_vwg = vp.n_chunks;
-        P.vis_ts = vd::vis_slots(vp.tmax) <= 2 ? 2 : 5;
-        c->vis_gm = vp.gm;
-        put(vp.wend.data(), 4 * vp.wend.size(), (void**)&P.vwend);
-        put(vp.vwg.data(), 4 * vp.vwg.size(), (void**)&P.vwg); put(vp.vrec.data(), 4 * vp.vrec.size(), (void**)&P.vrec);
-        put(vp.vlm.data(), 4 * vp.vlm.size(), (void**)&P.vlm); put(vp.vfac.data(), 4 * vp.vfac.size(), (void**)&P.vfac);
+        im.put(gl.data(), 4 * gl.size(), (void**)&P.glm_start); im.put(gac.data(), 4 * gac.size(), (void**)&P.glm_acol); im.put(gfc.data(), 4 * gfc.size(), (void**)&P.gfcol);
+        P.vis_f0 = vis_f0;
+    }
+    P.n_vwg = vp.n_chunks;
+    P.vis_ts = vd::vis_slots(vp.tmax) <= 2 ? 2 : 5;
+    c->vis_gm = vp.gm;
+    im.put(vp.wend.data(), 4 * vp.wend.size(), (void**)&P.vwend);
+    im.put(vp.vwg.data(), 4 * vp.vwg.size(), (void**)&P.vwg); im.put(vp.vrec.data(), 4 * vp.vrec.size(), (void**)&P.vrec);
+    im.put(vp.vlm.data(), 4 * vp.vlm.size(), (void**)&P.vlm); im.put(vp.vfac.data(), 4 * vp.vfac.size(), (void**)&P.vfac);
 #ifdef VIL_TUNING
-        put(nullptr, 8 * 2 * std::max(vp.rec_doubles, (size_t)16), (void**)&P.vpart);      // (x 2: the second half is the mirror of the record-traffic experiment, VIL_SKIP=1024 -- tuning build only)
-        P.vmirror = (long long)std::max(vp.rec_doubles, (size_t)16);
+    im.put(nullptr, 8 * 2 * std::max(vp.rec_doubles, (size_t)16), (void**)&P.vpart);      // (x 2: the second half is the mirror of the record-traffic experiment, VIL_SKIP=1024 -- tuning build only)
+    P.vmirror = (long long)std::max(vp.rec_doubles, (size_t)16);
 #else
-        put(nullptr, 8 * std::max(vp.rec_doubles, (size_t)16), (void**)&P.vpart);
+    im.put(nullptr, 8 * std::max(vp.rec_doubles, (size_t)16), (void**)&P.vpart);
 #endif
-    }
-    UPTICK("visual");
-    // LiDAR
-    {
-        std::vector<int> ch;
-        std::vector<int> lcp(2 * (K + 1), 0);   // chunk ranges per pose (chunks are pose-ordered): plane [0..K], edge [K+1..2K+1]
-        auto ranges = [&](const std::vector<int>& chunks, int base) {
-            std::vector<int> cnt(K + 1, 0);
-            for (size_t q = 0; q < chunks.size() / 3; ++q) cnt[chunks[3 * q + 2] + 1]++;
-            for (int k = 0; k < K; ++k) cnt[k + 1] += cnt[k];
-            for (int k = 0; k <= K; ++k) lcp[base + k] = cnt[k];
-        };
-        // device-resident tables (vil_internal.h): every factor sits on pose 0 in the caller's order -- only the chunk list is built here
-        auto chunks_pose0 = [&](int n) { ch.clear(); for (int s0 = 0; s0 < n; s0 += VIL_THREADS) { ch.push_back(s0); ch.push_back(std::min(VIL_THREADS, n - s0)); ch.push_back(0); } };
-        std::vector<int> cnt;
-        const bool res_lidar = p->n_plane == VIL_LIDAR_RESIDENT && p->n_edge == VIL_LIDAR_RESIDENT;
-        c->lidar_resident = res_lidar;
-        // resident frame slabs (vil_lidar_push): slab i belongs to pose K - count + i; only the chunk list is built here
-        auto chunks_slabs = [&](bool plane) {
-            ch.clear();
-            const int ns = (int)c->slabs.size();
-            for (int i = 0; i < ns; ++i) {
-                const int n = plane ? c->slabs[i].np : c->slabs[i].ne, cap = plane ? c->cap_p : c->cap_e, pose = K - ns + i;
-                for (int s0 = 0; s0 < n; s0 += VIL_THREADS) { ch.push_back(c->slabs[i].slot * cap + s0); ch.push_back(std::min(VIL_THREADS, n - s0)); ch.push_back(pose); }
-            }
-        };
-        int np_tot = p->n_plane, ne_tot = p->n_edge;
-        if (res_lidar) {
-            if ((int)c->slabs.size() > K) return VIL_ERR_UNSUPPORTED;
-            np_tot = ne_tot = 0;
-            for (auto& sl : c->slabs) { np_tot += sl.np; ne_tot += sl.ne; }
-        }
-        if (res_lidar) { chunks_slabs(true); c->plane_perm.clear(); put(nullptr, 8, (void**)&P.pl_c); }
-        else if (dl) { chunks_pose0(p->n_plane); c->plane_perm.clear(); put(nullptr, 8, (void**)&P.pl_c); }
+    return VIL_OK;
+}
+// LiDAR tables: the caller's points pose-sorted into SoA, or only the chunk lists (device-resident points, the context's slabs)
+static int upload_lidar(vil_ctx* c, ImageBuilder& im, const vil_problem* p, const vil_device_lidar* dl, DevP& P) {
+    const int K = p->K;
+    std::vector<int> ch, cnt;
+    std::vector<int> lcp(2 * (K + 1), 0);   // chunk ranges per pose (chunks are pose-ordered): plane [0..K], edge [K+1..2K+1]
+    const bool res_lidar = p->n_plane == VIL_LIDAR_RESIDENT && p->n_edge == VIL_LIDAR_RESIDENT;
+    c->lidar_resident = res_lidar;
+    // one kind of point factor (plane: 7 components, edge: 9): its chunk list, and for the caller's points the pose-sorted SoA table.  Only the chunk list for
+    // device-resident tables (vil_internal.h: every factor sits on pose 0 in the caller's order) and resident frame slabs (vil_lidar_push: slab i belongs to pose K - count + i)
+    auto kind = [&](bool plane, int n, const int* pose, const double* cst, std::vector<int>& perm, const double** soa, int* stride, int* nchunk, const int** tab, int base) {
+        const int ns = (int)c->slabs.size(), ncomp = plane ? 7 : 9;
+        ch.clear(); perm.clear();
+        if (res_lidar) for (int i = 0; i < ns; ++i) {
+            const int m = plane ? c->slabs[i].np : c->slabs[i].ne, cap = plane ? c->cap_p : c->cap_e;
+            for (int s0 = 0; s0 < m; s0 += VIL_THREADS) { ch.push_back(c->slabs[i].slot * cap + s0); ch.push_back(std::min(VIL_THREADS, m - s0)); ch.push_back(K - ns + i); }
+        } else if (dl) for (int s0 = 0; s0 < n; s0 += VIL_THREADS) { ch.push_back(s0); ch.push_back(std::min(VIL_THREADS, n - s0)); ch.push_back(0); }
+        if (res_lidar || dl) im.put(nullptr, 8, (void**)soa);
         else {
-            lidar_order(p->n_plane, p->plane_pose, K, c->plane_perm, cnt); lidar_chunks(cnt, K, ch);
-            P.pl_stride = (p->n_plane + 31) & ~31;
-            if (double* dst = (double*)reserve(8 * (size_t)7 * std::max(P.pl_stride, 1), (void**)&P.pl_c)) lidar_soa(p->n_plane, 7, p->plane_const, c->plane_perm, P.pl_stride, dst);
+            lidar_order(n, pose, K, perm, cnt); lidar_chunks(cnt, K, ch);
+            *stride = (n + 31) & ~31;
+            if (double* dst = (double*)im.reserve(8 * (size_t)ncomp * std::max(*stride, 1), (void**)soa)) lidar_soa(n, ncomp, cst, perm, *stride, dst);
         }
-        P.n_plane = np_tot; P.n_pchunk = (int)ch.size() / 3; ranges(ch, 0);
-        c->mm.lidar0 = false;
-        for (size_t q = 0; q < ch.size() / 3; ++q) if (ch[3 * q + 2] == 0) c->mm.lidar0 = true;
-        put(ch.data(), 4 * ch.size(), (void**)&P.pchunk);
-        if (res_lidar) { chunks_slabs(false); c->edge_perm.clear(); put(nullptr, 8, (void**)&P.ed_c); }
-        else if (dl) { chunks_pose0(p->n_edge); c->edge_perm.clear(); put(nullptr, 8, (void**)&P.ed_c); }
-        else {
-            lidar_order(p->n_edge, p->edge_pose, K, c->edge_perm, cnt); lidar_chunks(cnt, K, ch);
-            P.ed_stride = (p->n_edge + 31) & ~31;
-            if (double* dst = (double*)reserve(8 * (size_t)9 * std::max(P.ed_stride, 1), (void**)&P.ed_c)) lidar_soa(p->n_edge, 9, p->edge_const, c->edge_perm, P.ed_stride, dst);
-        }
-        P.n_edge = ne_tot; P.n_echunk = (int)ch.size() / 3; ranges(ch, K + 1);
-        for (size_t q = 0; q < ch.size() / 3; ++q) if (ch[3 * q + 2] == 0) c->mm.lidar0 = true;
-        put(ch.data(), 4 * ch.size(), (void**)&P.echunk);
-        // (resident slabs under a communicator: a frame with fewer points than ranks leaves some ranks' slices empty -- whether pose 0 carries LiDAR factors, and with it the
-        //  kept / dropped layout of the marginalisation every rank commits, is decided from the UNSLICED counts)
-        if (res_lidar) c->mm.lidar0 = (int)c->slabs.size() == K && c->slabs[0].np_all + c->slabs[0].ne_all > 0;
-        put(nullptr, 8 * (size_t)28 * std::max(P.n_pchunk + P.n_echunk, 1), (void**)&P.lpart);
-        put(lcp.data(), 4 * lcp.size(), (void**)&P.lchunk_pose);
-    }
-    UPTICK("lidar");
-    // IMU
+        *nchunk = (int)ch.size() / 3;
+        for (size_t q = 0; q < ch.size() / 3; ++q) { lcp[base + ch[3 * q + 2] + 1]++; if (ch[3 * q + 2] == 0) c->mm.lidar0 = true; }
+        for (int k = 0; k < K; ++k) lcp[base + k + 1] += lcp[base + k];
+        im.put(ch.data(), 4 * ch.size(), (void**)tab);
+    };
+    if (res_lidar && (int)c->slabs.size() > K) return VIL_ERR_UNSUPPORTED;
+    c->mm.lidar0 = false;
+    kind(true, p->n_plane, p->plane_pose, p->plane_const, c->plane_perm, &P.pl_c, &P.pl_stride, &P.n_pchunk, &P.pchunk, 0);
+    kind(false, p->n_edge, p->edge_pose, p->edge_const, c->edge_perm, &P.ed_c, &P.ed_stride, &P.n_echunk, &P.echunk, K + 1);
+    P.n_plane = p->n_plane; P.n_edge = p->n_edge;
+    if (res_lidar) { P.n_plane = P.n_edge = 0; for (auto& sl : c->slabs) { P.n_plane += sl.np; P.n_edge += sl.ne; } }
+    // (resident slabs under a communicator: a frame with fewer points than ranks leaves some ranks' slices empty -- whether pose 0 carries LiDAR factors, and with it the
+    //  kept / dropped layout of the marginalisation every rank commits, is decided from the UNSLICED counts)
+    if (res_lidar) c->mm.lidar0 = (int)c->slabs.size() == K && c->slabs[0].np_all + c->slabs[0].ne_all > 0;
+    im.put(nullptr, 8 * (size_t)28 * std::max(P.n_pchunk + P.n_echunk, 1), (void**)&P.lpart);
+    im.put(lcp.data(), 4 * lcp.size(), (void**)&P.lchunk_pose);
+    return VIL_OK;
+}
+// IMU, prior and ICP / LPS tables; pinv: reduced-system column -> prior column (-1: none)
+static int upload_imu_prior(vil_ctx* c, ImageBuilder& im, const vil_problem* p, const WinSrc* ws, DevP& P, std::vector<int>& pinv) {
+    const int K = p->K, D = 15 * K + 7;
     P.n_imu = p->n_imu;
-    if (ws) put(nullptr, 8 * (size_t)287 * std::max(p->n_imu, 1), (void**)&P.imu_c);      // gathered from the IMU slots by k_win_pack, like U
-    else put(p->imu_const, 8 * (size_t)287 * p->n_imu, (void**)&P.imu_c);
-    put(nullptr, 8 * (size_t)225 * std::max(p->n_imu, 1), (void**)&P.imu_U);
-    put(p->imu_i, 4 * (size_t)p->n_imu, (void**)&P.imu_i); put(p->imu_j, 4 * (size_t)p->n_imu, (void**)&P.imu_j);
-    put(nullptr, 8 * (size_t)931 * std::max(p->n_imu, 1), (void**)&P.ipart);
+    if (ws) im.put(nullptr, 8 * (size_t)287 * std::max(p->n_imu, 1), (void**)&P.imu_c);      // gathered from the IMU slots by k_win_pack, like U
+    else im.put(p->imu_const, 8 * (size_t)287 * p->n_imu, (void**)&P.imu_c);
+    im.put(nullptr, 8 * (size_t)225 * std::max(p->n_imu, 1), (void**)&P.imu_U);
+    im.put(p->imu_i, 4 * (size_t)p->n_imu, (void**)&P.imu_i); im.put(p->imu_j, 4 * (size_t)p->n_imu, (void**)&P.imu_j);
+    im.put(nullptr, 8 * (size_t)931 * std::max(p->n_imu, 1), (void**)&P.ipart);
     if (!c->d_imu_perm) {   // the order of an IMU role's record entries in a one-launch iteration: what the chain workgroup gathers first.  Constant: one device copy per context
         int perm[1024]; int n = VIL_CHAIN_REC;
         for (int e = 0; e < 931; ++e) { const int ce = chain_rec_index(e); if (ce >= 0) perm[ce] = e; else perm[n++] = e; }
@@ -962,12 +939,11 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
         HIPCHK(hipMemcpy(c->d_imu_perm, perm, sizeof(perm), hipMemcpyHostToDevice));
     }
     P.imu_perm = c->d_imu_perm;
-    put(nullptr, 4 * (size_t)(std::max(p->n_imu, 1) + 8), (void**)&P.cflag);
-    put(nullptr, 8 * (size_t)VIL_CHAIN_REC * std::max(p->n_imu, 1), (void**)&P.irec);      // (compact IMU records for the chain workgroup of a one-launch iteration)
-    // prior
+    im.put(nullptr, 4 * (size_t)(std::max(p->n_imu, 1) + 8), (void**)&P.cflag);
+    im.put(nullptr, 8 * (size_t)VIL_CHAIN_REC * std::max(p->n_imu, 1), (void**)&P.irec);      // (compact IMU records for the chain workgroup of a one-launch iteration)
     P.pn = p->prior.n > 0 ? p->prior.n : 0; P.pnblk = P.pn ? p->prior.nblk : 0;
     c->prior_joff.clear();
-    std::vector<int> pinv(D, -1);
+    pinv.assign(D, -1);
     if (P.pn) {
         const vil_prior& pr = p->prior;
         const int n = pr.n;
@@ -985,28 +961,30 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
             if (pr.blk_col[b] < 0 || pr.blk_col[b] + ls > n) return VIL_ERR_INVALID_ARGUMENT;
             for (int q = 0; q < ls; ++q) pmap[pr.blk_col[b] + q] = col < 0 ? -1 : col + q;
         }
-        put(pr.blk_kind, 4 * (size_t)pr.nblk, (void**)&P.pblk_kind); put(pr.blk_index, 4 * (size_t)pr.nblk, (void**)&P.pblk_index);
-        put(pr.blk_col, 4 * (size_t)pr.nblk, (void**)&P.pblk_col); put(xoff.data(), 4 * (size_t)pr.nblk, (void**)&P.pblk_xoff);
-        put(pmap.data(), 4 * (size_t)n, (void**)&P.pmap);
+        im.put(pr.blk_kind, 4 * (size_t)pr.nblk, (void**)&P.pblk_kind); im.put(pr.blk_index, 4 * (size_t)pr.nblk, (void**)&P.pblk_index);
+        im.put(pr.blk_col, 4 * (size_t)pr.nblk, (void**)&P.pblk_col); im.put(xoff.data(), 4 * (size_t)pr.nblk, (void**)&P.pblk_xoff);
+        im.put(pmap.data(), 4 * (size_t)n, (void**)&P.pmap);
         for (int q = 0; q < n; ++q) if (pmap[q] >= 0) pinv[pmap[q]] = q;
         if (!ws) {
-            put(pr.x0, 8 * (size_t)xo, (void**)&P.px0); put(pr.J0, 8 * (size_t)n * n, (void**)&P.pJ0); put(pr.r0, 8 * (size_t)n, (void**)&P.pr0);
-            put(nullptr, 8 * (size_t)n * n, (void**)&P.pH); put(nullptr, 8 * (size_t)n, (void**)&P.pg0); put(nullptr, 8, (void**)&P.pc0);
+            im.put(pr.x0, 8 * (size_t)xo, (void**)&P.px0); im.put(pr.J0, 8 * (size_t)n * n, (void**)&P.pJ0); im.put(pr.r0, 8 * (size_t)n, (void**)&P.pr0);
+            im.put(nullptr, 8 * (size_t)n * n, (void**)&P.pH); im.put(nullptr, 8 * (size_t)n, (void**)&P.pg0); im.put(nullptr, 8, (void**)&P.pc0);
         }
     }
-    put(pinv.data(), 4 * (size_t)D, (void**)&P.pinv);
-    put(nullptr, 8 * (size_t)((P.pn ? P.pn + 1 : 0) + 601 * (p->n_icp + p->n_lps) + 1), (void**)&P.mpart);
-    // ICP / LPS
+    im.put(pinv.data(), 4 * (size_t)D, (void**)&P.pinv);
+    im.put(nullptr, 8 * (size_t)((P.pn ? P.pn + 1 : 0) + 601 * (p->n_icp + p->n_lps) + 1), (void**)&P.mpart);
     P.n_icp = p->n_icp; P.n_lps = p->n_lps;
-    put(p->icp_ids, 16 * (size_t)p->n_icp, (void**)&P.icp_ids); put(p->icp_const, 80 * (size_t)p->n_icp, (void**)&P.icp_c);
-    put(p->lps_ids, 8 * (size_t)p->n_lps, (void**)&P.lps_ids); put(p->lps_const, 56 * (size_t)p->n_lps, (void**)&P.lps_c);
-    UPTICK("imu+prior");
-    // systems + work space (zero-initialised)
+    im.put(p->icp_ids, 16 * (size_t)p->n_icp, (void**)&P.icp_ids); im.put(p->icp_const, 80 * (size_t)p->n_icp, (void**)&P.icp_c);
+    im.put(p->lps_ids, 8 * (size_t)p->n_lps, (void**)&P.lps_ids); im.put(p->lps_const, 56 * (size_t)p->n_lps, (void**)&P.lps_c);
+    return VIL_OK;
+}
+// systems + work space (zero-initialised); returns the doubles of a system set's camera part
+static size_t upload_workspace(vil_ctx* c, ImageBuilder& im, const WinSrc* ws, const vil_problem* gp, bool sharded, DevP& P) {
+    const int K = P.K, L = P.L, D = P.D, NV = P.NV;
     // one contiguous block per set: [S | gred | bc | diag | cost | 2 spare | hll | bl | invp | sl | eA | eO]
-    const size_t Lp = (size_t)std::max(L, 1), Fp = (size_t)std::max(gp ? (ws ? ws->n_vis_all : gp->n_vis) : n_vis, 1);
+    const size_t Lp = (size_t)std::max(L, 1), Fp = (size_t)std::max(gp ? (ws ? ws->n_vis_all : gp->n_vis) : P.n_vis, 1);
     const size_t ar_cam = ((size_t)D * D + 3 * (size_t)D + 3 + 1) & ~size_t(1);
     c->span = ar_cam + 4 * Lp + 13 * Lp + 6 * Fp;
-    for (int q = 0; q < 2; ++q) put(nullptr, 8 * c->span, (void**)&P.sys[q].ar);
+    for (int q = 0; q < 2; ++q) im.put(nullptr, 8 * c->span, (void**)&P.sys[q].ar);
     P.rank = sharded ? c->rank : 0; P.world = sharded ? c->world : 1;
     for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
     c->graphs.clear(); c->solves_since_upload = 0;
@@ -1014,159 +992,126 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
     // multi-GPU plumbing (set 0 = this rank's partial system, all-reduced into set 1, which the step kernel reads); vil_debug_set_split
     // runs it on a single rank (tests)
     c->split = c->sharded || c->force_split;
-    put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.Sl); put(nullptr, 8 * (size_t)D, (void**)&P.Sc); put(nullptr, 8 * (size_t)D, (void**)&P.dc); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.dl);
-    put(nullptr, 8 * (size_t)D, (void**)&P.gradc); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.gradl); put(nullptr, 8 * (size_t)D, (void**)&P.gnc); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.gnl);
-    { const size_t Tm = (size_t)(D + 16) / 16; put(nullptr, 8 * std::max((size_t)D * D, (size_t)TILE_SZ * (Tm * (Tm + 1) / 2)), (void**)&P.M); } put(nullptr, 16 * (size_t)D, (void**)&P.stepc);      // (two 64-bit words per value: half + launch epoch)
-    put(nullptr, 8 * 4 * 16, (void**)&P.hpart); put(nullptr, 4 * 16, (void**)&P.hflag);
-    put(nullptr, 8 * 8 * 16 * 8, (void**)&P.hpart2); put(nullptr, 4 * 16 * 8, (void**)&P.hflag2);      // one slot per helper WAVE
-    put(nullptr, 16, (void**)&P.xflag); put(nullptr, 16, (void**)&P.xstat);
-    put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.la); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.lb); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.stepl);
-    put(nullptr, 8 * (size_t)D, (void**)&P.tmpc); put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.tmpl);
-    put(nullptr, sizeof(Ctl), (void**)&P.ctl);
-    put(nullptr, 8 * 64, (void**)&P.dbg);
-    // ---- chain eliminated ahead of the step kernel (vil_prechain.hpp): every IMU factor joins frames (k, k+1), at most one per pair, single GPU.
-    //      The gather table is built here once per upload: the chain workgroup then sums <= 3 sources per entry in a fixed order.
-    bool pre_ok = !sharded && !c->force_split && c->launch_mode != 2 && L >= 0 && K >= 3 && VIL_TUNE_ENV("VIL_NO_PRECHAIN") == nullptr;
+    im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.Sl); im.put(nullptr, 8 * (size_t)D, (void**)&P.Sc); im.put(nullptr, 8 * (size_t)D, (void**)&P.dc); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.dl);
+    im.put(nullptr, 8 * (size_t)D, (void**)&P.gradc); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.gradl); im.put(nullptr, 8 * (size_t)D, (void**)&P.gnc); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.gnl);
+    { const size_t Tm = (size_t)(D + 16) / 16; im.put(nullptr, 8 * std::max((size_t)D * D, (size_t)TILE_SZ * (Tm * (Tm + 1) / 2)), (void**)&P.M); } im.put(nullptr, 16 * (size_t)D, (void**)&P.stepc);      // (two 64-bit words per value: half + launch epoch)
+    im.put(nullptr, 8 * 4 * 16, (void**)&P.hpart); im.put(nullptr, 4 * 16, (void**)&P.hflag);
+    im.put(nullptr, 8 * 8 * 16 * 8, (void**)&P.hpart2); im.put(nullptr, 4 * 16 * 8, (void**)&P.hflag2);      // one slot per helper WAVE
+    im.put(nullptr, 16, (void**)&P.xflag); im.put(nullptr, 16, (void**)&P.xstat);
+    im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.la); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.lb); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.stepl);
+    im.put(nullptr, 8 * (size_t)D, (void**)&P.tmpc); im.put(nullptr, 8 * (size_t)std::max(L, 1), (void**)&P.tmpl);
+    im.put(nullptr, sizeof(Ctl), (void**)&P.ctl);
+    im.put(nullptr, 8 * 64, (void**)&P.dbg);
+    im.put(nullptr, 8 * (size_t)vd::chain_wcols(K) * vd::chain_rs(K), (void**)&P.chW);      // (the chain eliminated ahead of the step kernel: chain_table)
+    im.put(nullptr, 8 * (size_t)54 * K, (void**)&P.chLdg); im.put(nullptr, 8 * (size_t)82 * K, (void**)&P.chLsb); im.put(nullptr, 8 * (size_t)136 * K, (void**)&P.chLraw);
+    im.put(nullptr, 8 * (size_t)9 * K, (void**)&P.chSc); im.put(nullptr, 8 * (size_t)9 * K, (void**)&P.chDc);
+    im.put(nullptr, 8 * (size_t)2 * (NV + 1), (void**)&P.chZ); im.put(nullptr, 8 * 4, (void**)&P.chQ); im.put(nullptr, 16, (void**)&P.chOk);
+    im.put(nullptr, 4 * (size_t)(gather_blocks(D, NV, RED_EPW, false) + 8), (void**)&P.gflag);      // (one flag per gather workgroup of the merged launch: never more than the gather kernel has)
+    im.put(nullptr, 64, (void**)&P.chflag); im.put(nullptr, 4 * 64, (void**)&P.wwflag); im.put(nullptr, 4 * (size_t)(K + 8), (void**)&P.swflag);
+    im.put(nullptr, 4 * 64, (void**)&P.sall);
+    im.put(nullptr, 4 * (size_t)VIL_SFLAG_MAX, (void**)&P.sflag);      // one flag per sweep workgroup of a one-launch iteration (taken only when there are fewer: below)
+    im.put(nullptr, 256, (void**)&P.ihdr); im.put(nullptr, 8 * 2 * (size_t)(16 * K + 8), (void**)&P.xtag);
+    im.put(nullptr, 64, (void**)&P.abortf);      // (raised by a wait on another workgroup's flag that gives up: vil_math.hpp, spin_until_eq)
+    { const size_t Tp = (size_t)(NV + 1 + 15) / 16; im.put(nullptr, 8 * (size_t)TILE_SZ * (Tp * (Tp + 1) / 2), (void**)&P.chWW); }
+    im.put(nullptr, 8 * (size_t)VIL_CHC_MAX, (void**)&P.chc);
+    return ar_cam;
+}
+// ---- chain eliminated ahead of the step kernel (vil_prechain.hpp): every IMU factor joins frames (k, k+1), at most one per pair, single GPU.
+//      The gather table is built here once per upload: the chain workgroup then sums <= 3 sources per entry in a fixed order.  built: a new table went up.
+static int chain_table(vil_ctx* c, const vil_problem* p, bool sharded, DevP& P, const std::vector<int>& pinv, bool& pre_ok, bool& built) {
+    const int K = P.K, L = P.L, D = P.D, NV = P.NV;
+    pre_ok = !sharded && !c->force_split && c->launch_mode != 2 && L >= 0 && K >= 3 && VIL_TUNE_ENV("VIL_NO_PRECHAIN") == nullptr;
     std::vector<int> as_i(K, -1), as_j(K, -1);
     for (int f = 0; f < p->n_imu && pre_ok; ++f) {
         const int i = p->imu_i[f], j = p->imu_j[f];
         if (j != i + 1 || as_i[i] >= 0 || as_j[j] >= 0) pre_ok = false; else { as_i[i] = f; as_j[j] = f; }
     }
-    {
-        const int rs = vd::chain_rs(K);
-        put(nullptr, 8 * (size_t)vd::chain_wcols(K) * rs, (void**)&P.chW);
-        put(nullptr, 8 * (size_t)54 * K, (void**)&P.chLdg); put(nullptr, 8 * (size_t)82 * K, (void**)&P.chLsb); put(nullptr, 8 * (size_t)136 * K, (void**)&P.chLraw);
-        put(nullptr, 8 * (size_t)9 * K, (void**)&P.chSc); put(nullptr, 8 * (size_t)9 * K, (void**)&P.chDc);
-        put(nullptr, 8 * (size_t)2 * (NV + 1), (void**)&P.chZ); put(nullptr, 8 * 4, (void**)&P.chQ); put(nullptr, 16, (void**)&P.chOk);
-        put(nullptr, 4 * (size_t)(gather_blocks(D, NV, RED_EPW, false) + 8), (void**)&P.gflag);      // (one flag per gather workgroup of the merged launch: never more than the gather kernel has)
-        put(nullptr, 64, (void**)&P.chflag); put(nullptr, 4 * 64, (void**)&P.wwflag); put(nullptr, 4 * (size_t)(K + 8), (void**)&P.swflag);
-        put(nullptr, 4 * 64, (void**)&P.sall);
-        put(nullptr, 4 * (size_t)VIL_SFLAG_MAX, (void**)&P.sflag);      // one flag per sweep workgroup of a one-launch iteration (taken only when there are fewer: below)
-        put(nullptr, 256, (void**)&P.ihdr); put(nullptr, 8 * 2 * (size_t)(16 * K + 8), (void**)&P.xtag);
-        put(nullptr, 64, (void**)&P.abortf);      // (raised by a wait on another workgroup's flag that gives up: vil_math.hpp, spin_until_eq)
-        { const size_t Tp = (size_t)(NV + 1 + 15) / 16; put(nullptr, 8 * (size_t)TILE_SZ * (Tp * (Tp + 1) / 2), (void**)&P.chWW); }
-        put(nullptr, 8 * (size_t)VIL_CHC_MAX, (void**)&P.chc);
-    }
-    UPTICK("ws-puts");
-    if (pre_ok) {
-        // the table depends on K, the IMU factor layout and the prior's block structure only: consecutive windows of a tracker share it, so it
-        // lives in its own device buffer and is rebuilt (and sent) only when that key changes
-        std::vector<int> key; key.reserve(2 * K + D + 2);
-        key.push_back(K); key.push_back(P.pn); key.insert(key.end(), as_i.begin(), as_i.end()); key.insert(key.end(), as_j.begin(), as_j.end()); key.insert(key.end(), pinv.begin(), pinv.end());
-        int cs = -1;
-        for (int q = 0; q < 4; ++q) if (c->chtabs[q].d && c->chtabs[q].key == key) cs = q;
-        const bool ct_hit = cs >= 0;
-        if (!ct_hit) { cs = 0; for (int q = 1; q < 4; ++q) if (c->chtabs[q].used < c->chtabs[cs].used) cs = q; }      // (least recently used)
-        vil_ctx::ChTab& ct = c->chtabs[cs];
-        ct.used = ++c->chtab_clock; c->chtab_cur = cs;
-        if (!ct_hit) {
-            const int NPs = vd::chain_slab_nps(K), pn = P.pn;
-            const int o_dg = 0, o_sub = vd::even_up(45 * K), o_pbc = o_sub + vd::even_up(81 * K), o_pp = o_pbc + 162 * K, o_rhs = o_pp + CHAIN_NPC_MAX * NPs;
-            std::vector<int> tab, pq(9 * K, -1);
-            int npc = 0;
-            for (int jc = 0; jc < 9 * K; ++jc) if (pn > 0 && pinv[NV + jc] >= 0) pq[jc] = npc++;
-            if (npc > CHAIN_NPC_MAX) pre_ok = false;       // (cannot happen: the prior's speed-bias blocks are neighbours -- checked for the chain path)
-            auto ip = [&](int f, int la, int lb) { return f < 0 ? -1 : f * 931 + la * 30 + lb; };
-            auto pr = [&](int r, int col) { if (pn <= 0) return -1; const int pi = pinv[r], pj = pinv[col]; return (pi >= 0 && pj >= 0) ? pi * pn + pj : -1; };
-            // (IMU sources carry two indices: (index into the 931-double records + 1) in the low half, (index into the compact records of a one-launch iteration + 1) in the high half; 0: none)
-            auto both = [&](int a) { if (a < 0) return 0; const int f = a / 931, ce = chain_rec_index(a % 931); return (a + 1) | ((f * VIL_CHAIN_REC + ce + 1) << 16); };
-            auto emit = [&](int dst, int a, int b, int cc) { if (a < 0 && b < 0 && cc == -1) return; tab.push_back(dst); tab.push_back(both(a)); tab.push_back(both(b)); tab.push_back(cc); };
-            for (int k = 0; k < K && pre_ok; ++k) {
-                const int fi = as_i[k], fj = as_j[k];
-                for (int i = 0; i < 9; ++i) for (int j = 0; j <= i; ++j) emit(o_dg + 45 * k + i * (i + 1) / 2 + j, ip(fi, 6 + i, 6 + j), ip(fj, 21 + i, 21 + j), pr(NV + 9 * k + i, NV + 9 * k + j));
-                if (k + 1 < K) for (int q = 0; q < 9; ++q) for (int cc = 0; cc < 9; ++cc) emit(o_sub + 81 * k + q * 9 + cc, ip(fi, 21 + q, 6 + cc), -1, pr(NV + 9 * (k + 1) + q, NV + 9 * k + cc));
-                for (int cc = 0; cc < 9; ++cc) {
-                    const int pj = pn > 0 ? pinv[NV + 9 * k + cc] : -1;
-                    emit(o_rhs + 9 * k + cc, fi < 0 ? -1 : fi * 931 + 900 + 6 + cc, fj < 0 ? -1 : fj * 931 + 900 + 21 + cc, pj >= 0 ? -pj - 2 : -1);
-                    for (int d = 0; d < 3; ++d) {              // pose rows of frames k-1, k, k+1: the IMU factors' share, compact
-                        const int fr = k - 1 + d;
-                        if (fr < 0 || fr >= K) continue;
-                        for (int lr = 0; lr < 6; ++lr) {
-                            const int a = (fi >= 0 && (fr == k || fr == k + 1)) ? ip(fi, fr == k ? lr : 15 + lr, 6 + cc) : -1;
-                            const int b = (fj >= 0 && (fr == k - 1 || fr == k)) ? ip(fj, fr == k - 1 ? lr : 15 + lr, 21 + cc) : -1;
-                            emit(o_pbc + ((k * 3 + d) * 6 + lr) * 9 + cc, a, b, -1);
-                        }
+    if (!pre_ok) return VIL_OK;
+    // the table depends on K, the IMU factor layout and the prior's block structure only: consecutive windows of a tracker share it, so it
+    // lives in its own device buffer and is rebuilt (and sent) only when that key changes
+    std::vector<int> key; key.reserve(2 * K + D + 2);
+    key.push_back(K); key.push_back(P.pn); key.insert(key.end(), as_i.begin(), as_i.end()); key.insert(key.end(), as_j.begin(), as_j.end()); key.insert(key.end(), pinv.begin(), pinv.end());
+    int cs = -1;
+    for (int q = 0; q < 4; ++q) if (c->chtabs[q].d && c->chtabs[q].key == key) cs = q;
+    const bool ct_hit = cs >= 0;
+    if (!ct_hit) { cs = 0; for (int q = 1; q < 4; ++q) if (c->chtabs[q].used < c->chtabs[cs].used) cs = q; }      // (least recently used)
+    vil_ctx::ChTab& ct = c->chtabs[cs];
+    ct.used = ++c->chtab_clock; c->chtab_cur = cs;
+    if (!ct_hit) {
+        const int NPs = vd::chain_slab_nps(K), pn = P.pn;
+        const int o_dg = 0, o_sub = vd::even_up(45 * K), o_pbc = o_sub + vd::even_up(81 * K), o_pp = o_pbc + 162 * K, o_rhs = o_pp + CHAIN_NPC_MAX * NPs;
+        std::vector<int> tab, pq(9 * K, -1);
+        int npc = 0;
+        for (int jc = 0; jc < 9 * K; ++jc) if (pn > 0 && pinv[NV + jc] >= 0) pq[jc] = npc++;
+        if (npc > CHAIN_NPC_MAX) pre_ok = false;       // (cannot happen: the prior's speed-bias blocks are neighbours -- checked for the chain path)
+        auto ip = [&](int f, int la, int lb) { return f < 0 ? -1 : f * 931 + la * 30 + lb; };
+        auto pr = [&](int r, int col) { if (pn <= 0) return -1; const int pi = pinv[r], pj = pinv[col]; return (pi >= 0 && pj >= 0) ? pi * pn + pj : -1; };
+        // (IMU sources carry two indices: (index into the 931-double records + 1) in the low half, (index into the compact records of a one-launch iteration + 1) in the high half; 0: none)
+        auto both = [&](int a) { if (a < 0) return 0; const int f = a / 931, ce = chain_rec_index(a % 931); return (a + 1) | ((f * VIL_CHAIN_REC + ce + 1) << 16); };
+        auto emit = [&](int dst, int a, int b, int cc) { if (a < 0 && b < 0 && cc == -1) return; tab.push_back(dst); tab.push_back(both(a)); tab.push_back(both(b)); tab.push_back(cc); };
+        for (int k = 0; k < K && pre_ok; ++k) {
+            const int fi = as_i[k], fj = as_j[k];
+            for (int i = 0; i < 9; ++i) for (int j = 0; j <= i; ++j) emit(o_dg + 45 * k + i * (i + 1) / 2 + j, ip(fi, 6 + i, 6 + j), ip(fj, 21 + i, 21 + j), pr(NV + 9 * k + i, NV + 9 * k + j));
+            if (k + 1 < K) for (int q = 0; q < 9; ++q) for (int cc = 0; cc < 9; ++cc) emit(o_sub + 81 * k + q * 9 + cc, ip(fi, 21 + q, 6 + cc), -1, pr(NV + 9 * (k + 1) + q, NV + 9 * k + cc));
+            for (int cc = 0; cc < 9; ++cc) {
+                const int pj = pn > 0 ? pinv[NV + 9 * k + cc] : -1;
+                emit(o_rhs + 9 * k + cc, fi < 0 ? -1 : fi * 931 + 900 + 6 + cc, fj < 0 ? -1 : fj * 931 + 900 + 21 + cc, pj >= 0 ? -pj - 2 : -1);
+                for (int d = 0; d < 3; ++d) {              // pose rows of frames k-1, k, k+1: the IMU factors' share, compact
+                    const int fr = k - 1 + d;
+                    if (fr < 0 || fr >= K) continue;
+                    for (int lr = 0; lr < 6; ++lr) {
+                        const int a = (fi >= 0 && (fr == k || fr == k + 1)) ? ip(fi, fr == k ? lr : 15 + lr, 6 + cc) : -1;
+                        const int b = (fj >= 0 && (fr == k - 1 || fr == k)) ? ip(fj, fr == k - 1 ? lr : 15 + lr, 21 + cc) : -1;
+                        emit(o_pbc + ((k * 3 + d) * 6 + lr) * 9 + cc, a, b, -1);
                     }
-                    if (pq[9 * k + cc] >= 0) for (int r = 0; r < NV; ++r) emit(o_pp + pq[9 * k + cc] * NPs + r, -1, -1, pr(r, NV + 9 * k + cc));      // the prior's share: every row
                 }
+                if (pq[9 * k + cc] >= 0) for (int r = 0; r < NV; ++r) emit(o_pp + pq[9 * k + cc] * NPs + r, -1, -1, pr(r, NV + 9 * k + cc));      // the prior's share: every row
             }
-            {   // the chain workgroup deals consecutive entries to consecutive threads and every entry has its own target: sorted by source address, a wave's loads of
-                // the IMU records (and of the prior) fall into a few cache lines each instead of one line per lane -- the gather is bound by the lines its loads touch
-                const size_t ne = tab.size() / 4;
-                std::vector<std::array<int, 4>> ent(ne);
-                memcpy(ent.data(), tab.data(), 16 * ne);
-                auto skey = [](const std::array<int, 4>& e) -> long long { return e[1] > 0 ? (e[1] >> 16) : e[2] > 0 ? (e[2] >> 16) : (1LL << 40) + (e[3] >= 0 ? (1LL << 32) + e[3] : -e[3]); };
-                std::stable_sort(ent.begin(), ent.end(), [&](const std::array<int, 4>& x, const std::array<int, 4>& y) { return skey(x) < skey(y); });
-                memcpy(tab.data(), ent.data(), 16 * ne);
-            }
-            tab.insert(tab.end(), pq.begin(), pq.end());       // behind the table: the chain column -> prior column map
-            while (tab.size() & 3) tab.push_back(0);
-            const size_t bytes = 4 * tab.size();
-            if (ct.ev_pending) { HIPCHK(hipEventSynchronize(ct.ev)); ct.ev_pending = false; }      // the previous table's DMA has left the pinned copy
-            if (bytes > ct.cap) {
-                HIPCHK(hipStreamSynchronize(c->stream));      // (nobody reads the old one)
-                if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h);
-                ct.d = nullptr; ct.h = nullptr; ct.cap = 0;
-                HIPCHK(hipMalloc((void**)&ct.d, 2 * bytes)); HIPCHK(hipHostMalloc((void**)&ct.h, 2 * bytes, hipHostMallocDefault));
-                ct.cap = 2 * bytes;
-            }
-            memcpy(ct.h, tab.data(), bytes);
-            HIPCHK(hipMemcpyAsync(ct.d, ct.h, bytes, hipMemcpyHostToDevice, c->stream));
-            if (!ct.ev) HIPCHK(hipEventCreateWithFlags(&ct.ev, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ct.ev, c->stream)); ct.ev_pending = true;
-            ct.n = ((int)tab.size() - ((9 * K + 3) & ~3)) / 4; ct.key.swap(key);
-            UPTICK("chtab-new");
         }
-        P.n_chtab = ct.n;
-        if (ct.n > VIL_CHC_MAX) pre_ok = false;
+        {   // the chain workgroup deals consecutive entries to consecutive threads and every entry has its own target: sorted by source address, a wave's loads of
+            // the IMU records (and of the prior) fall into a few cache lines each instead of one line per lane -- the gather is bound by the lines its loads touch
+            const size_t ne = tab.size() / 4;
+            std::vector<std::array<int, 4>> ent(ne);
+            memcpy(ent.data(), tab.data(), 16 * ne);
+            auto skey = [](const std::array<int, 4>& e) -> long long { return e[1] > 0 ? (e[1] >> 16) : e[2] > 0 ? (e[2] >> 16) : (1LL << 40) + (e[3] >= 0 ? (1LL << 32) + e[3] : -e[3]); };
+            std::stable_sort(ent.begin(), ent.end(), [&](const std::array<int, 4>& x, const std::array<int, 4>& y) { return skey(x) < skey(y); });
+            memcpy(tab.data(), ent.data(), 16 * ne);
+        }
+        tab.insert(tab.end(), pq.begin(), pq.end());       // behind the table: the chain column -> prior column map
+        while (tab.size() & 3) tab.push_back(0);
+        const size_t bytes = 4 * tab.size();
+        if (ct.ev_pending) { HIPCHK(hipEventSynchronize(ct.ev)); ct.ev_pending = false; }      // the previous table's DMA has left the pinned copy
+        if (bytes > ct.cap) {
+            HIPCHK(hipStreamSynchronize(c->stream));      // (nobody reads the old one)
+            if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h);
+            ct.d = nullptr; ct.h = nullptr; ct.cap = 0;
+            HIPCHK(hipMalloc((void**)&ct.d, 2 * bytes)); HIPCHK(hipHostMalloc((void**)&ct.h, 2 * bytes, hipHostMallocDefault));
+            ct.cap = 2 * bytes;
+        }
+        memcpy(ct.h, tab.data(), bytes);
+        HIPCHK(hipMemcpyAsync(ct.d, ct.h, bytes, hipMemcpyHostToDevice, c->stream));
+        if (!ct.ev) HIPCHK(hipEventCreateWithFlags(&ct.ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ct.ev, c->stream)); ct.ev_pending = true;
+        ct.n = ((int)tab.size() - ((9 * K + 3) & ~3)) / 4; ct.key.swap(key);
+        built = true;
     }
-    if (const char* ev = VIL_TUNE_ENV("VIL_SKIP")) P.skip_mask = atoi(ev);
-    // helper workgroups of the step kernel: worth it once every master thread would own more than one landmark
-    // (a helper keeps its landmarks' rows in registers between its two passes while it has at least one thread per landmark -- vil_step.hpp, lm_rows_quad:
-    //  up to 1920 landmarks a QUAD of threads per landmark, 128 landmarks per helper; beyond that a PAIR, 256 per helper; at most 15 helpers, so past
-    //  3840 landmarks a helper's threads loop over its slice)
-    P.n_help = vil_helpers_for(L);
-    if (const char* ev = VIL_TUNE_ENV("VIL_HELP")) P.n_help = std::max(0, std::min(15, atoi(ev)));
-    // master and helpers wait for one another inside the launch: all of them must be resident at once (vil_coop.hpp).  With its
-    // dynamic LDS a step workgroup owns a compute unit; a device with fewer units than 1 + n_help runs without helpers.
-    {
-        int cus = 0;
-        cus = vilcoop::compute_units(c->device);      // (what this process really has: a CU mask is not in the device attribute)
-        if (1 + P.n_help > cus / 2) P.n_help = 0;
-    }
-    UPTICK("workspace");
-    // device allocation + single H2D copy
-    if (oom) return VIL_ERR_DEVICE;
+    P.n_chtab = ct.n;
+    if (ct.n > VIL_CHC_MAX) pre_ok = false;
+    return VIL_OK;
+}
+// device allocation + single H2D copy: every slot of the image, the pointers that are not the arena's, the system sets; the parameter block goes to c->P
+static int commit(vil_ctx* c, ImageBuilder& im, DevP& P, bool pre_ok, const vil_device_lidar* dl, const vil_problem* gp, const WinSrc* ws, size_t ar_cam) {
+    Arena& ar = c->ar;
+    if (im.oom) return VIL_ERR_DEVICE;
     const size_t tables = (ar.hsize + 255) & ~size_t(255), total = tables + ((ar.ssize + 255) & ~size_t(255));
     if (total > ar.cap) { if (ar.d) HIPCHK(hipFree(ar.d)); ar.d = nullptr; ar.cap = 0; HIPCHK(hipMalloc(&ar.d, total + total / 4)); ar.cap = total + total / 4; }
-    for (const Fix& f : fix) *f.slot = ar.d + (f.scratch ? tables : 0) + f.off;
+    for (const ImageBuilder::Fix& f : im.fix) *f.slot = ar.d + (f.scratch ? tables : 0) + f.off;
     if (dl) { P.pl_c = dl->plane_soa; P.pl_stride = dl->plane_stride; P.ed_c = dl->edge_soa; P.ed_stride = dl->edge_stride; }
     if (!gp) { P.glm_start = P.lm_start; P.glm_acol = P.lm_acol; P.gfcol = P.fcol; }
     if (pre_ok) { const vil_ctx::ChTab& ct = c->chtabs[c->chtab_cur]; P.chtab = ct.d; P.chpq = ct.d + 4 * (size_t)ct.n; }
     if (c->lidar_resident) { P.pl_c = c->d_pl; P.pl_stride = c->nslot * c->cap_p; P.ed_c = c->d_ed; P.ed_stride = c->nslot * c->cap_e; }
     if (ws && P.pn) { P.px0 = ws->px0; P.pJ0 = ws->pJ0; P.pr0 = ws->pr0; P.pH = ws->pH; P.pg0 = ws->pg0; P.pc0 = ws->pc0; }      // the device prior slot, contractions included
-    {   // what vil_marginalize_resident will need (a few passes over int tables)
-        vil_ctx::MargMeta& mm = c->mm;
-        const vil_problem* const lp = p;                  // this rank's shard (LiDAR points of pose 0 of a resident window: from the unsliced slab counts, above)
-        if (gp) p = gp;                                    // which blocks the collected factors touch is a property of the WHOLE window, the same on every rank
-        mm.has_prior = p->prior.n > 0; mm.prior_kind.clear(); mm.prior_index.clear();
-        if (mm.has_prior) { mm.prior_kind.assign(p->prior.blk_kind, p->prior.blk_kind + p->prior.nblk); mm.prior_index.assign(p->prior.blk_index, p->prior.blk_index + p->prior.nblk); }
-        mm.obs0.assign(K, 0); mm.n_lm0 = 0; mm.imu01 = false; mm.use_td = p->use_td != 0;
-        if (ws) {
-            for (int l = 0; l < L; ++l) if (ws->lm_startf[l] == 0) { ++mm.n_lm0; for (int q = 1; q < ws->lm_nobs[l]; ++q) mm.obs0[q] = 1; }
-            for (int f = 0; f < p->n_imu; ++f) if (p->imu_i[f] == 0 && p->imu_j[f] == 1 && ws->sum_dt[ws->islot[1]] < 10.0) mm.imu01 = true;
-        } else {
-            int last_l = -1;
-            for (int f = 0; f < p->n_vis; ++f) if (p->vis_i[f] == 0) { mm.obs0[p->vis_j[f]] = 1; if (p->vis_l[f] != last_l) { ++mm.n_lm0; last_l = p->vis_l[f]; } }
-            for (int f = 0; f < p->n_imu; ++f) if (p->imu_i[f] == 0 && p->imu_j[f] == 1 && p->imu_const[(size_t)f * 287 + 16] < 10.0) mm.imu01 = true;
-        }
-        mm.icp_ids.assign(p->icp_ids, p->icp_ids + 4 * (size_t)p->n_icp); mm.lps_ids.assign(p->lps_ids, p->lps_ids + 2 * (size_t)p->n_lps);
-        if (!c->lidar_resident && !dl) {
-            for (int f = 0; f < p->n_plane && !mm.lidar0; ++f) if (p->plane_pose[f] == 0) mm.lidar0 = true;
-            for (int f = 0; f < p->n_edge && !mm.lidar0; ++f) if (p->edge_pose[f] == 0) mm.lidar0 = true;
-        }
-        p = lp;
-    }
+    const size_t Lp = (size_t)std::max(P.L, 1), D = P.D;
     for (int q = 0; q < 2; ++q) {
         SysBuf& sb = P.sys[q];
         sb.S = sb.ar; sb.gred = sb.S + (size_t)D * D; sb.bc = sb.gred + D; sb.diag = sb.bc + D; sb.cost = sb.diag + D;
@@ -1179,158 +1124,163 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
     }
     if (ar.ssize) HIPCHK(hipMemsetAsync(ar.d + tables, 0, ar.ssize, c->stream));
     P.drop_role = -1; P.drop_launch = -1;
-    c->P = P; c->K = K; c->L = L; c->D = D; c->NS = NS;
+    c->P = P; c->K = P.K; c->L = P.L; c->D = P.D; c->NS = P.NS;
     c->mirror_state = false;
-    if (!c->no_poll) { const int ms = ensure_mirror(c, (size_t)NS); if (ms != VIL_OK) return ms; }
+    if (!c->no_poll) { const int ms = ensure_mirror(c, (size_t)P.NS); if (ms != VIL_OK) return ms; }
     c->P.hctl = c->d_hctl; c->P.hseq = c->d_hseq; c->P.hstate = c->d_hstate;
     c->P.xorig = c->d_x0; c->P.gauge_on = c->gauge_on ? 1 : 0; c->P.setup_stat = c->d_status;
-    {
-        const int per = VIL_SWEEP_THREADS / 256;
-        auto nsw = [&](int R) { return P.n_imu + P.n_vwg + (P.n_pchunk + per * R - 1) / (per * R) + (P.n_echunk + per * R - 1) / (per * R) + 2; };
-        // (LiDAR workgroups can make several passes of two chunks -- fewer, longer workgroups when a window has more sweep roles than the device has compute units.
-        //  Measured at configs[2], 496 sweep roles: 1 pass 1068 us per 13-iteration solve, 2 passes 1085, 4 passes 1120, 8 passes 1282: the dispatcher's second round
-        //  balances better than any static packing.  One pass; the knob stays in the tuning build.)
-        int R = 1;
-        if (const char* ev = VIL_TUNE_ENV("VIL_LIDAR_REP")) R = std::max(1, atoi(ev));
-        P.lidar_rep = R; c->P.lidar_rep = R;
-        c->n_blocks_sweep = nsw(R);
+    return VIL_OK;
+}
+// what vil_marginalize_resident will need (a few passes over int tables; LiDAR points of pose 0 of a resident window: upload_lidar, from the unsliced slab counts)
+static void marg_meta(vil_ctx* c, const vil_problem* p, const vil_problem* gp, const WinSrc* ws, const vil_device_lidar* dl) {
+    vil_ctx::MargMeta& mm = c->mm;
+    if (gp) p = gp;                                    // which blocks the collected factors touch is a property of the WHOLE window, the same on every rank
+    mm.has_prior = p->prior.n > 0; mm.prior_kind.clear(); mm.prior_index.clear();
+    if (mm.has_prior) { mm.prior_kind.assign(p->prior.blk_kind, p->prior.blk_kind + p->prior.nblk); mm.prior_index.assign(p->prior.blk_index, p->prior.blk_index + p->prior.nblk); }
+    mm.obs0.assign(c->K, 0); mm.n_lm0 = 0; mm.imu01 = false; mm.use_td = p->use_td != 0;
+    if (ws) {
+        for (int l = 0; l < c->L; ++l) if (ws->lm_startf[l] == 0) { ++mm.n_lm0; for (int q = 1; q < ws->lm_nobs[l]; ++q) mm.obs0[q] = 1; }
+        for (int f = 0; f < p->n_imu; ++f) if (p->imu_i[f] == 0 && p->imu_j[f] == 1 && ws->sum_dt[ws->islot[1]] < 10.0) mm.imu01 = true;
+    } else {
+        int last_l = -1;
+        for (int f = 0; f < p->n_vis; ++f) if (p->vis_i[f] == 0) { mm.obs0[p->vis_j[f]] = 1; if (p->vis_l[f] != last_l) { ++mm.n_lm0; last_l = p->vis_l[f]; } }
+        for (int f = 0; f < p->n_imu; ++f) if (p->imu_i[f] == 0 && p->imu_j[f] == 1 && p->imu_const[(size_t)f * 287 + 16] < 10.0) mm.imu01 = true;
     }
+    mm.icp_ids.assign(p->icp_ids, p->icp_ids + 4 * (size_t)p->n_icp); mm.lps_ids.assign(p->lps_ids, p->lps_ids + 2 * (size_t)p->n_lps);
+    if (!c->lidar_resident && !dl) {
+        for (int f = 0; f < p->n_plane && !mm.lidar0; ++f) if (p->plane_pose[f] == 0) mm.lidar0 = true;
+        for (int f = 0; f < p->n_edge && !mm.lidar0; ++f) if (p->edge_pose[f] == 0) mm.lidar0 = true;
+    }
+}
+// ---- THE launch structure of the uploaded window, into c->ls and the fields of c->P that carry it: the kernels of an iteration, their grids and dynamic LDS
+//      (granted here), the co-residency checks (probed here).  Every launch, the ladder of vil_solve_resident and vil_solve_batch read c->ls.
+static int choose_structure(vil_ctx* c, const vil_problem* p, bool pre_ok) {
+    DevP& P = c->P;
+    Structure& S = c->ls;
+    S = Structure();
+    const int K = P.K, D = P.D, NV = P.NV;
+    // (LiDAR workgroups can make several passes of two chunks -- fewer, longer workgroups when a window has more sweep roles than the device has compute units.
+    //  Measured at configs[2], 496 sweep roles: 1 pass 1068 us per 13-iteration solve, 2 passes 1085, 4 passes 1120, 8 passes 1282: the dispatcher's second round
+    //  balances better than any static packing.  One pass; the knob stays in the tuning build.)
+    int R = 1;
+    if (const char* ev = VIL_TUNE_ENV("VIL_LIDAR_REP")) R = std::max(1, atoi(ev));
+    P.lidar_rep = R;
+    const int per = VIL_SWEEP_THREADS / 256;
+    S.n_sweep = P.n_imu + P.n_vwg + (P.n_pchunk + per * R - 1) / (per * R) + (P.n_echunk + per * R - 1) / (per * R) + 2;
     // visual workgroups: the staged factors, the landmark records, the dense operand rows of the largest chunk
-    c->lds_sweep = sizeof(double) * (size_t)(VIS_LDS_FIXED + c->vis_gm);
-    if (c->lds_sweep < 8 * 2048) c->lds_sweep = 8 * 2048;
-    if (c->lds_sweep > 160 * 1024) return VIL_ERR_UNSUPPORTED;
-    auto grant_sweep = [&]() -> int {
-        const int v = P.vis_ts == 2 ? 0 : 1;
-        if ((int)c->lds_sweep > c->attr_sweep[v]) { HIPCHK(hipFuncSetAttribute(v ? (const void*)k_sweep<5> : (const void*)k_sweep<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_sweep)); c->attr_sweep[v] = (int)c->lds_sweep; }
-        return VIL_OK;
-    };
-    { const int gs = grant_sweep(); if (gs != VIL_OK) return gs; }
-    c->n_blocks_reduce = gather_blocks(D, NV, RED_EPW, false);
+    S.lds_sweep = sizeof(double) * (size_t)(VIS_LDS_FIXED + c->vis_gm);
+    if (S.lds_sweep < 8 * 2048) S.lds_sweep = 8 * 2048;
+    if (S.lds_sweep > 160 * 1024) return VIL_ERR_UNSUPPORTED;
+    S.sweep_fn = P.vis_ts == 5 ? (const void*)k_sweep<5> : (const void*)k_sweep<2>;
+    HIPCHK(grant_lds(c, S.sweep_fn, S.lds_sweep));
+    S.n_reduce = gather_blocks(D, NV, RED_EPW, false);
     // ---- step kernel variant: the speed-bias part of the reduced matrix is a chain whenever every IMU factor couples (k, k+1)
     //      and the prior's speed-bias blocks are neighbours (VINS: exactly one) -> vil_chain.hpp; anything else: dense path
-    {
-        bool chain = VIL_TUNE_ENV("VIL_DENSE_STEP") == nullptr;
-        for (int f = 0; f < p->n_imu && chain; ++f) if (std::abs(p->imu_i[f] - p->imu_j[f]) > 1) chain = false;
-        if (P.pn) {
-            std::vector<int> psb;
-            for (int b = 0; b < p->prior.nblk; ++b) if (p->prior.blk_kind[b] == VIL_BLK_SPEEDBIAS) psb.push_back(p->prior.blk_index[b]);
-            for (int a : psb) for (int b : psb) if (std::abs(a - b) > 1) chain = false;
+    bool chain = VIL_TUNE_ENV("VIL_DENSE_STEP") == nullptr;
+    for (int f = 0; f < p->n_imu && chain; ++f) if (std::abs(p->imu_i[f] - p->imu_j[f]) > 1) chain = false;
+    if (P.pn) {
+        std::vector<int> psb;
+        for (int b = 0; b < p->prior.nblk; ++b) if (p->prior.blk_kind[b] == VIL_BLK_SPEEDBIAS) psb.push_back(p->prior.blk_index[b]);
+        for (int a : psb) for (int b : psb) if (std::abs(a - b) > 1) chain = false;
+    }
+    S.chain_rs = vd::chain_rs(K);
+    const size_t Tp = (size_t)(NV + 1 + 15) / 16, tiles = (size_t)TILE_SZ * (Tp * (Tp + 1) / 2);
+    const int Tw = (int)(Tp * (Tp + 1) / 2);
+    if (chain) {
+        const size_t wt = (size_t)vd::chain_wcols(K) * S.chain_rs, scr = vd::chain_scratch_doubles(K);
+        const size_t fixed = step_static_lds((const void*)k_step<true, 1>) + 256;      // (the kernel's whole static LDS: StepShared + the gather / tile roles' scratch)
+        if (8 * (tiles + wt + scr) + fixed <= 160 * 1024) { S.chain = 1; S.lds_step = 8 * (tiles + wt + scr); }
+        else if (8 * (tiles + scr) + fixed <= 160 * 1024) { S.chain = 2; S.lds_step = 8 * (tiles + scr); }
+    }
+    // one GPU, chain windows: gather + step in ONE launch with the chain eliminated beside the gather (prechain 1, vil_prechain.hpp).
+    // Until round 4 only up to K = 12: with ~100 kB of dynamic LDS per workgroup the ~1500 gather workgroups of a K = 20 window needed six rounds
+    // on 256 compute units.  Windows the launch cannot hold (capacity check below) keep the separate gather and eliminate the chain inside
+    // k_sweep, behind the IMU / prior workgroups' flags, with the W W^T tiles on extra workgroups of k_reduce (prechain 2).
+    const size_t lds3 = 8 * (tiles + 54 * (size_t)K + 82 * (size_t)K + vd::even_up(9 * K) + 16), ldsc = 8 * vd::prechain_lds_doubles(K);
+    const bool can_pre = !c->split && pre_ok && S.chain != 0 && Tp * (Tp + 1) / 2 <= 64 && lds3 + step_static_lds((const void*)k_step<true, 3>) + 256 <= 160 * 1024 && ldsc <= 150 * 1024;
+    // (round 4: every window size -- the gather of a prechain solve forms the visual sub-space only, 551 workgroups at K = 20 instead of 1500)
+    int kmerge = 20;
+    if (const char* ev = VIL_TUNE_ENV("VIL_MERGE_K")) kmerge = atoi(ev);
+    bool merged = can_pre && (c->launch_mode == 0 || c->launch_mode == 3 || c->launch_mode == 4) && K <= kmerge && std::max(lds3, ldsc) + step_static_lds((const void*)k_step<true, 3>) + 256 <= 160 * 1024 && VIL_TUNE_ENV("VIL_NO_MERGE") == nullptr;
+    // the merged launch holds workgroups that spin on flags (master, helpers, one per W W^T tile) next to the finite ones they wait for (chain,
+    // gather: lower block indices, dispatched first).  It is only taken when the device can hold every spinning workgroup AND one more at the
+    // same time -- otherwise the waiters could occupy every slot before the last gather workgroup has found one (vil_coop.hpp)
+    if (merged && !fits_per_xcd(1 + P.n_help + Tw + 1, coop_capacity(c, (const void*)k_step<true, 3>, std::max(lds3, ldsc)))) merged = false;
+    S.prechain = merged ? 1 : (can_pre ? 2 : 0);
+    if (S.prechain) {
+        S.chain = 3;
+        S.n_ww = Tw;
+        if (merged) S.lds_step = std::max(lds3, ldsc);       // (the chain workgroup is one of the merged launch's)
+        else {
+            S.lds_step = lds3;
+            S.lds_sweep = std::max(S.lds_sweep, ldsc);      // the chain workgroup rides in k_sweep
+            HIPCHK(grant_lds(c, S.sweep_fn, S.lds_sweep));
+            S.n_sweep += 1;
         }
-        P.chain = 0; P.chain_rs = vd::chain_rs(K);
-        if (chain) {
-            const size_t Tp = (size_t)(NV + 1 + 15) / 16, tiles = (size_t)TILE_SZ * (Tp * (Tp + 1) / 2), wt = (size_t)vd::chain_wcols(K) * P.chain_rs, scr = vd::chain_scratch_doubles(K);
-            const size_t fixed = step_static_lds((const void*)k_step<true, 1>) + 256;      // (the kernel's whole static LDS: StepShared + the gather / tile roles' scratch)
-            if (8 * (tiles + wt + scr) + fixed <= 160 * 1024) { P.chain = 1; c->lds_step = 8 * (tiles + wt + scr); }
-            else if (8 * (tiles + scr) + fixed <= 160 * 1024) { P.chain = 2; c->lds_step = 8 * (tiles + scr); }
-        }
-        // one GPU, chain windows: gather + step in ONE launch with the chain eliminated beside the gather (prechain 1, vil_prechain.hpp).
-        // Until round 4 only up to K = 12: with ~100 kB of dynamic LDS per workgroup the ~1500 gather workgroups of a K = 20 window needed six rounds
-        // on 256 compute units.  Windows the launch cannot hold (capacity check below) keep the separate gather and eliminate the chain inside
-        // k_sweep, behind the IMU / prior workgroups' flags, with the W W^T tiles on extra workgroups of k_reduce (prechain 2).
-        const size_t Tp_ = (size_t)(NV + 1 + 15) / 16, tiles_ = (size_t)TILE_SZ * (Tp_ * (Tp_ + 1) / 2);
-        const size_t lds3 = 8 * (tiles_ + 54 * (size_t)K + 82 * (size_t)K + vd::even_up(9 * K) + 16), ldsc = 8 * vd::prechain_lds_doubles(K);
-        const bool can_pre = !c->split && pre_ok && P.chain != 0 && Tp_ * (Tp_ + 1) / 2 <= 64 && lds3 + step_static_lds((const void*)k_step<true, 3>) + 256 <= 160 * 1024 && ldsc <= 150 * 1024;
-        // (round 4: every window size -- the gather of a prechain solve forms the visual sub-space only, 551 workgroups at K = 20 instead of 1500)
-        int kmerge = 20;
-        if (const char* ev = VIL_TUNE_ENV("VIL_MERGE_K")) kmerge = atoi(ev);
-        bool merged = can_pre && (c->launch_mode == 0 || c->launch_mode == 3 || c->launch_mode == 4) && K <= kmerge && std::max(lds3, ldsc) + step_static_lds((const void*)k_step<true, 3>) + 256 <= 160 * 1024 && VIL_TUNE_ENV("VIL_NO_MERGE") == nullptr;
-        if (merged) {
-            // the merged launch holds workgroups that spin on flags (master, helpers, one per W W^T tile) next to the finite ones they wait for (chain,
-            // gather: lower block indices, dispatched first).  It is only taken when the device can hold every spinning workgroup AND one more at the
-            // same time -- otherwise the waiters could occupy every slot before the last gather workgroup has found one (vil_coop.hpp)
-            // (keyed by the LDS size: 42 kB at K = 10 is three workgroups per compute unit, 95 kB at K = 20 one -- a context that uploads a small window first must not check a large one against the small one's capacity)
-            const size_t ldsm = std::max(lds3, ldsc);
-            if (c->cap_step3 < 0 || c->cap_step3_lds != ldsm) { c->cap_step3 = vilcoop::capacity((const void*)k_step<true, 3>, VIL_STEP_THREADS, ldsm, c->device); c->cap_step3_lds = ldsm; }
-            const int Tw = (int)(Tp_ * (Tp_ + 1) / 2);
-            if (!fits_per_xcd(1 + P.n_help + Tw + 1, c->cap_step3)) merged = false;
-        }
-        P.prechain = merged ? 1 : (can_pre ? 2 : 0);
-        c->n_ww = 0;
-        if (P.prechain) {
-            P.chain = 3;
-            c->n_ww = (int)(Tp_ * (Tp_ + 1) / 2);
-            if (merged) c->lds_step = std::max(lds3, ldsc);       // (the chain workgroup is one of the merged launch's)
-            else {
-                c->lds_step = lds3;
-                c->lds_sweep = std::max(c->lds_sweep, ldsc);      // the chain workgroup rides in k_sweep
-                { const int gs = grant_sweep(); if (gs != VIL_OK) return gs; }
-                c->n_blocks_sweep += 1;
-            }
-        }
-        c->P.chain = P.chain; c->P.chain_rs = P.chain_rs; c->P.prechain = P.prechain;
-        // (the merged launch gathers 64 entries per 512-thread workgroup: half as many workgroups as the gather kernel's)
-        const bool g64 = VIL_TUNE_ENV("VIL_GATHER32") == nullptr;
-        c->n_gather_m = g64 ? gather_blocks(D, NV, 64, true) : gather_blocks(D, NV, RED_EPW, true);
-        c->n_blocks_reduce_po = gather_blocks(D, NV, RED_EPW, true);
-        c->P.rs_merged = merged ? (g64 ? 2 : 1) : 0; c->P.n_ww = c->n_ww; c->P.n_gather = merged ? c->n_gather_m : 0;
-        // ---- the whole iteration in ONE launch (k_iter, vil_iter.hpp): whenever the merged gather + step launch is taken, the kernel's single dynamic-LDS size
-        //      (the larger of the sweep roles' and the step roles' needs -- StepShared and the gather / tile scratch are carved from it) fits a compute unit, and
-        //      the device holds the workgroups that wait for one another (master, helpers, tiles) at once.  vil_debug_set_launch_mode(3) keeps the two launches.
-        c->fused = false; c->persist = false; c->P.n_sw = 0;
-        if (merged && g64 && (c->launch_mode == 0 || c->launch_mode == 4) && c->n_blocks_sweep <= VIL_SFLAG_MAX && VIL_TUNE_ENV("VIL_NO_FUSE") == nullptr) {
-            const size_t scratch = 8 * (size_t)(2 * VIS_TAB + 2 * 8 * (VIL_STEP_THREADS / 8) + 160);      // gather role: descriptor table | part[2][512] | index tables | red
-            const size_t step_need = 8 * (size_t)VIL_SS_DOUBLES + std::max(std::max(lds3, ldsc), scratch);
-            const size_t li = std::max(c->lds_sweep, step_need);
-            const int v = P.vis_ts == 2 ? 0 : 1;
-            const void* fn = v ? (const void*)k_iter<5> : (const void*)k_iter<2>;
-            if (li <= 160 * 1024) {
-                if ((int)li > c->attr_iter[v]) { HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)li)); c->attr_iter[v] = (int)li; }
-                if (c->cap_iter[v] < 0 || c->cap_iter_lds[v] != li) { c->cap_iter[v] = vilcoop::capacity(fn, VIL_STEP_THREADS, li, c->device); c->cap_iter_lds[v] = li; }
-                const int Tw = (int)(Tp_ * (Tp_ + 1) / 2);
-                if (fits_per_xcd(1 + P.n_help + Tw + 1, c->cap_iter[v])) { c->fused = true; c->lds_iter = li; c->P.n_sw = c->n_blocks_sweep; }      // (+ the chain workgroup)
-                // ---- the whole SOLVE in one resident launch (k_solve): the grid [sweep roles | chain | master | helpers | tiles] must fit the device at once with two
-                //      workgroups to spare, and every gather item must find a workgroup that takes it as a duty (tiles, helpers, sweep roles): configs[1]-sized
-                //      windows.  Everything else keeps one launch per iteration.  vil_debug_set_launch_mode(4) keeps k_iter.
-                if (c->fused && c->launch_mode == 0 && VIL_TUNE_ENV("VIL_NO_PERSIST") == nullptr) {
-                    const size_t sweep_need = 8 * (size_t)(VIL_LC_DOUBLES + VIL_XL_DOUBLES) + std::max(c->lds_sweep, 8 * (size_t)2048 + scratch);      // [Ctl copy | state copy | role arrays (IMU roles: gather scratch behind them)]
-                    const size_t ls = std::max(sweep_need, step_need);
-                    const void* fs = vil_k_solve_fn(P.vis_ts);
-                    if (ls <= 160 * 1024 && K <= 15) {
-                        if ((int)ls > c->attr_solve[v]) { HIPCHK(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls)); c->attr_solve[v] = (int)ls; }
-                        if (c->cap_solve[v] < 0 || c->cap_solve_lds[v] != ls) { c->cap_solve[v] = vilcoop::capacity(fs, VIL_STEP_THREADS, ls, c->device); c->cap_solve_lds[v] = ls; }
-                        const int grid = c->n_blocks_sweep + 2 + P.n_help + Tw, n_cap = c->n_blocks_sweep + P.n_help + Tw;
-                        if (fits_per_xcd(grid, c->cap_solve[v]) && c->n_gather_m <= n_cap) { c->persist = true; c->lds_solve = ls; }
-                    }
+    }
+    // (the merged launch gathers 64 entries per 512-thread workgroup: half as many workgroups as the gather kernel's)
+    const bool g64 = VIL_TUNE_ENV("VIL_GATHER32") == nullptr;
+    S.n_gather_m = g64 ? gather_blocks(D, NV, 64, true) : gather_blocks(D, NV, RED_EPW, true);
+    S.n_reduce_po = gather_blocks(D, NV, RED_EPW, true);
+    S.rs_merged = merged ? (g64 ? 2 : 1) : 0; S.n_gather = merged ? S.n_gather_m : 0;
+    // ---- the whole iteration in ONE launch (k_iter, vil_iter.hpp): whenever the merged gather + step launch is taken, the kernel's single dynamic-LDS size
+    //      (the larger of the sweep roles' and the step roles' needs -- StepShared and the gather / tile scratch are carved from it) fits a compute unit, and
+    //      the device holds the workgroups that wait for one another (master, helpers, tiles) at once.  vil_debug_set_launch_mode(3) keeps the two launches.
+    if (merged && g64 && (c->launch_mode == 0 || c->launch_mode == 4) && S.n_sweep <= VIL_SFLAG_MAX && VIL_TUNE_ENV("VIL_NO_FUSE") == nullptr) {
+        const size_t scratch = 8 * (size_t)(2 * VIS_TAB + 2 * 8 * (VIL_STEP_THREADS / 8) + 160);      // gather role: descriptor table | part[2][512] | index tables | red
+        const size_t step_need = 8 * (size_t)VIL_SS_DOUBLES + std::max(std::max(lds3, ldsc), scratch);
+        const size_t li = std::max(S.lds_sweep, step_need);
+        const void* fn = P.vis_ts == 5 ? (const void*)k_iter<5> : (const void*)k_iter<2>;
+        if (li <= 160 * 1024) {
+            HIPCHK(grant_lds(c, fn, li));
+            const int cap = coop_capacity(c, fn, li);
+            if (fits_per_xcd(1 + P.n_help + Tw + 1, cap)) { S.fused = true; S.iter_fn = fn; S.lds_iter = li; S.n_sw = S.n_sweep; S.cap_fused = cap; }      // (+ the chain workgroup)
+            // ---- the whole SOLVE in one resident launch (k_solve): the grid [sweep roles | chain | master | helpers | tiles] must fit the device at once with two
+            //      workgroups to spare, and every gather item must find a workgroup that takes it as a duty (tiles, helpers, sweep roles): configs[1]-sized
+            //      windows.  Everything else keeps one launch per iteration.  vil_debug_set_launch_mode(4) keeps k_iter.
+            if (S.fused && c->launch_mode == 0 && VIL_TUNE_ENV("VIL_NO_PERSIST") == nullptr) {
+                const size_t sweep_need = 8 * (size_t)(VIL_LC_DOUBLES + VIL_XL_DOUBLES) + std::max(S.lds_sweep, 8 * (size_t)2048 + scratch);      // [Ctl copy | state copy | role arrays (IMU roles: gather scratch behind them)]
+                const size_t ls = std::max(sweep_need, step_need);
+                const void* fs = vil_k_solve_fn(P.vis_ts);
+                if (ls <= 160 * 1024 && K <= 15) {
+                    HIPCHK(grant_lds(c, fs, ls));
+                    const int grid = S.n_sweep + 2 + P.n_help + Tw, n_cap = S.n_sweep + P.n_help + Tw;
+                    if (fits_per_xcd(grid, coop_capacity(c, fs, ls)) && S.n_gather_m <= n_cap) { S.persist = true; S.lds_solve = ls; }
                 }
             }
         }
     }
-    if (P.chain) {
-        c->step_lds = true;
-        if (P.chain == 3) {
-            if ((int)c->lds_step > c->attr_step[4]) { HIPCHK(hipFuncSetAttribute((const void*)k_step<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_step)); c->attr_step[4] = (int)c->lds_step; }
-        } else if (P.chain == 1) {
-            if ((int)c->lds_step > c->attr_step[1]) { HIPCHK(hipFuncSetAttribute((const void*)k_step<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_step)); c->attr_step[1] = (int)c->lds_step; }
-        } else {
-            if ((int)c->lds_step > c->attr_step[2]) { HIPCHK(hipFuncSetAttribute((const void*)k_step<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_step)); c->attr_step[2] = (int)c->lds_step; }
-        }
-    } else {
-    { const size_t T = (size_t)(D + 1 + 15) / 16; c->lds_step = 8 * TILE_SZ * (T * (T + 1) / 2); }   // 16x16-tiled (row stride 17) lower storage incl. the rhs row
-    c->step_lds = c->lds_step + step_static_lds((const void*)k_step<true, 0>) + 256 <= 160 * 1024;
-    if (c->step_lds) {
-        if ((int)c->lds_step > c->attr_step[0]) { HIPCHK(hipFuncSetAttribute((const void*)k_step<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_step)); c->attr_step[0] = (int)c->lds_step; }
-    } else {
-        // tile array in global memory; LDS stages the active tile column of the factorisation (T tiles)
+    P.chain = S.chain; P.chain_rs = S.chain_rs; P.prechain = S.prechain; P.rs_merged = S.rs_merged; P.n_ww = S.n_ww; P.n_gather = S.n_gather; P.n_sw = S.n_sw;
+    static const void* const chain_step[4] = {nullptr, (const void*)k_step<true, 1>, (const void*)k_step<true, 2>, (const void*)k_step<true, 3>};
+    S.step_fn = chain_step[S.chain];
+    if (!S.chain) {
         const size_t T = (size_t)(D + 1 + 15) / 16;
-        c->lds_step = 8 * (size_t)TILE_SZ * T;
-        if (c->lds_step + step_static_lds((const void*)k_step<false, 0>) + 256 > 160 * 1024) return VIL_ERR_UNSUPPORTED;
-        if ((int)c->lds_step > c->attr_step[3]) { HIPCHK(hipFuncSetAttribute((const void*)k_step<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_step)); c->attr_step[3] = (int)c->lds_step; }
+        S.lds_step = 8 * TILE_SZ * (T * (T + 1) / 2);      // 16x16-tiled (row stride 17) lower storage incl. the rhs row
+        S.step_fn = (const void*)k_step<true, 0>;
+        if (S.lds_step + step_static_lds(S.step_fn) + 256 > 160 * 1024) {
+            S.lds_step = 8 * (size_t)TILE_SZ * T;      // tile array in global memory; LDS stages the active tile column of the factorisation (T tiles)
+            S.step_fn = (const void*)k_step<false, 0>;
+            if (S.lds_step + step_static_lds(S.step_fn) + 256 > 160 * 1024) return VIL_ERR_UNSUPPORTED;
+        }
     }
-    }
-    UPTICK("h2d+attrs");
-    // one-time set-up: IMU sqrt-information, prior contraction
+    HIPCHK(grant_lds(c, S.step_fn, S.lds_step));
+    return VIL_OK;
+}
+// one-time set-up: IMU sqrt-information, prior contraction
+static int upload_setup(vil_ctx* c, const WinSrc* ws, bool check_setup, const int* wd_track, const int* wd_startf) {
+    const DevP& P = c->P;
     if (!ws) HIPCHK(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));      // (resident window: nothing writes it -- its status word is the window's own, vil_win_solve -- and a 4-byte fill is a 5 us launch)
     if (ws) {
         // resident window: expand the landmark table into the factor tables, gather the IMU records, copy the state -- everything k_setup
         // would compute (sqrt-information, prior contractions) already sits next to its source
         WinPack W; memset(&W, 0, sizeof W);
-        W.L = L; W.F = n_vis; W.stride = P.vis_stride; W.T = ws->T;
+        W.L = P.L; W.F = P.n_vis; W.stride = P.vis_stride; W.T = ws->T;
         W.lm_start = P.lm_start; W.lm_track = wd_track; W.lm_startf = wd_startf; W.store = ws->d_store;
-        for (int k = 0; k < K; ++k) { W.fslot[k] = ws->fslot[k]; W.islot[k] = ws->islot[k]; }
+        for (int k = 0; k < P.K; ++k) { W.fslot[k] = ws->fslot[k]; W.islot[k] = ws->islot[k]; }
         W.vis_c = const_cast<double*>(P.vis_c); W.vis_i = const_cast<int*>(P.vis_i); W.vis_j = const_cast<int*>(P.vis_j); W.vis_l = const_cast<int*>(P.vis_l); W.fcol = const_cast<int*>(P.fcol); W.vfinv = P.vfinv;
         W.n_imu = P.n_imu; W.rec = ws->d_rec; W.U = ws->d_U; W.imu_c = const_cast<double*>(P.imu_c); W.imu_U = const_cast<double*>(P.imu_U);
-        W.NS = NS; W.x0 = P.x[0]; W.x1 = P.x[1]; W.xorig = c->d_x0;
-        const int nbf = (n_vis + 255) / 256, nbs = (NS + 255) / 256;
+        W.NS = P.NS; W.x0 = P.x[0]; W.x1 = P.x[1]; W.xorig = c->d_x0;
+        const int nbf = (P.n_vis + 255) / 256, nbs = (P.NS + 255) / 256;
         hipLaunchKernelGGL(k_win_pack, dim3(nbf + P.n_imu + nbs), dim3(256), 0, c->stream, W, nbf);
     }
     const int nb_setup = ws ? 0 : P.n_imu + (P.pn ? 64 : 0);
@@ -1342,6 +1292,52 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
         HIPCHK(hipGetLastError());
         if (c->h_word[0] != 0) return VIL_ERR_NOT_POSITIVE_DEFINITE;
     }
+    return VIL_OK;
+}
+
+// check_setup: wait for k_setup's verdict (an IMU covariance that is not positive definite) and return it; false: nothing is waited for --
+// the first step kernel of the solve ends it with that status (DevP::setup_stat), and the launches of the solve queue up behind the upload
+static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, bool sharded, const vil_device_lidar* dl = nullptr, const vil_problem* gp = nullptr, int vis_f0 = 0, bool check_setup = true, const WinSrc* ws = nullptr) {
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    int st = validate(p, s, dl != nullptr, ws != nullptr);
+    if (st != VIL_OK) return st;                 // an invalid problem leaves the resident one untouched
+    c->uploaded = false;                         // from here on the arena is rewritten: resident only again after a complete upload
+    c->resident_kind = 0; c->reset_pending = false;
+    HIPCHK(hipSetDevice(c->device));
+#ifdef VIL_TUNING
+    static const bool up_trace = getenv("VIL_UPLOAD_TRACE") != nullptr;
+    auto up_t0 = std::chrono::steady_clock::now();
+    #define UPTICK(name) do { if (up_trace) { const auto t_ = std::chrono::steady_clock::now(); fprintf(stderr, "[upload] %-10s %7.1f us\n", name, std::chrono::duration<double, std::micro>(t_ - up_t0).count()); up_t0 = t_; } } while (0)
+#else
+    #define UPTICK(name) do {} while (0)
+#endif
+    if (c->up_pending) { HIPCHK(hipEventSynchronize(c->up_ev)); c->up_pending = false; }
+    c->ar.reset();
+    ImageBuilder im{c->ar};
+    DevP P; memset(&P, 0, sizeof P);
+    upload_state(c, im, p, s, ws, P);
+    UPTICK("head");
+    int* wd_track = nullptr; int* wd_startf = nullptr;       // device copies of the landmark table (resident window)
+    if ((st = upload_visual(c, im, p, ws, gp, vis_f0, P, &wd_track, &wd_startf)) != VIL_OK) return st;
+    UPTICK("visual");
+    if ((st = upload_lidar(c, im, p, dl, P)) != VIL_OK) return st;
+    UPTICK("lidar");
+    std::vector<int> pinv;
+    if ((st = upload_imu_prior(c, im, p, ws, P, pinv)) != VIL_OK) return st;
+    UPTICK("imu+prior");
+    const size_t ar_cam = upload_workspace(c, im, ws, gp, sharded, P);
+    UPTICK("ws-puts");
+    bool pre_ok = false, built = false;
+    if ((st = chain_table(c, p, sharded, P, pinv, pre_ok, built)) != VIL_OK) return st;
+    if (built) UPTICK("chtab-new");
+    if (const char* ev = VIL_TUNE_ENV("VIL_SKIP")) P.skip_mask = atoi(ev);
+    P.n_help = vil_helpers_for(P.L, c->device);
+    UPTICK("workspace");
+    if ((st = commit(c, im, P, pre_ok, dl, gp, ws, ar_cam)) != VIL_OK) return st;
+    marg_meta(c, p, gp, ws, dl);
+    if ((st = choose_structure(c, p, pre_ok)) != VIL_OK) return st;
+    UPTICK("h2d+attrs");
+    if ((st = upload_setup(c, ws, check_setup, wd_track, wd_startf)) != VIL_OK) return st;
     UPTICK("setup");
     c->uploaded = true; c->resident_kind = 2;    // vil_upload / vil_solve promote it to 1
     return VIL_OK;
@@ -1539,9 +1535,13 @@ static DevP view(const vil_ctx* c, int which) {
     if (c->split) { P.sys[0] = P.sys[1] = c->P.sys[which]; if (which == 1) { P.rank = 0; P.world = 1; } }
     return P;
 }
+// launches of the kernels choose_structure picked (k_sweep, k_iter, k_step take (DevP, SolveOpts))
+static void launch_chosen(vil_ctx* c, const void* fn, unsigned grid, unsigned threads, size_t lds, DevP P, SolveOpts so) {
+    void* args[] = {&P, &so};
+    hipLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, c->stream);
+}
 static int launch_sweep(vil_ctx* c, const SolveOpts& so) {
-    if (c->P.vis_ts == 2) hipLaunchKernelGGL(k_sweep<2>, dim3(c->n_blocks_sweep), dim3(VIL_SWEEP_THREADS), c->lds_sweep, c->stream, view(c, 0), so);
-    else hipLaunchKernelGGL(k_sweep<5>, dim3(c->n_blocks_sweep), dim3(VIL_SWEEP_THREADS), c->lds_sweep, c->stream, view(c, 0), so);
+    launch_chosen(c, c->ls.sweep_fn, c->ls.n_sweep, VIL_SWEEP_THREADS, c->ls.lds_sweep, view(c, 0), so);
     return VIL_OK;
 }
 // one trust-region iteration as ONE launch (vil_iter.hpp); only un-sharded solves of a window the upload marked `fused`
@@ -1549,28 +1549,27 @@ static int launch_iter(vil_ctx* c, const SolveOpts& so) {
     DevP Pi = c->P;
     Pi.gather_pose_only = 1;
     Pi.prof = c->profiling ? c->d_prof : nullptr; Pi.wg_launch = c->profiling ? c->wg_launch : -1;
-    const dim3 g(c->n_blocks_sweep + 1 + c->n_gather_m + 1 + c->P.n_help + c->n_ww), b(VIL_STEP_THREADS);      // [sweep roles | chain | master | helpers | W W^T tiles | gather]
-    if (c->P.vis_ts == 2) hipLaunchKernelGGL(k_iter<2>, g, b, c->lds_iter, c->stream, Pi, so);
-    else hipLaunchKernelGGL(k_iter<5>, g, b, c->lds_iter, c->stream, Pi, so);
+    launch_chosen(c, c->ls.iter_fn, c->ls.n_sweep + 1 + c->ls.n_gather_m + 1 + c->P.n_help + c->ls.n_ww, VIL_STEP_THREADS, c->ls.lds_iter, Pi, so);      // [sweep roles | chain | master | helpers | W W^T tiles | gather]
     return VIL_OK;
 }
 // the whole solve as ONE resident launch (vil_iter.hpp, k_solve); budget_ticks: what is left of max_time_s on the device's 100 MHz clock (0: no cap)
 static int launch_solve(vil_ctx* c, const SolveOpts& so, long long budget_ticks) {
     DevP Pi = c->P;
     Pi.gather_pose_only = 1; Pi.prof = c->stamps ? c->d_prof : nullptr; Pi.wg_launch = -1; Pi.persist = 1;
-    vil_k_solve_launch(c->P.vis_ts, (unsigned)(c->n_blocks_sweep + 2 + c->P.n_help + c->n_ww), c->lds_solve, c->stream, Pi, so, budget_ticks);      // [sweep roles | chain | master | helpers | W W^T tiles]
+    vil_k_solve_launch(c->P.vis_ts, (unsigned)(c->ls.n_sweep + 2 + c->P.n_help + c->ls.n_ww), c->ls.lds_solve, c->stream, Pi, so, budget_ticks);      // [sweep roles | chain | master | helpers | W W^T tiles]
     return VIL_OK;
 }
 static int launch_reduce_step(vil_ctx* c, const SolveOpts& so, bool step, hipEvent_t ev_mid = nullptr, hipEvent_t ev_coll = nullptr) {
-    const bool merged = step && c->P.rs_merged;          // one GPU: the gather rides in the step kernel's launch (vil_step.hpp)
+    const Structure& S = c->ls;
+    const bool merged = step && S.rs_merged;          // one GPU: the gather rides in the step kernel's launch (vil_step.hpp)
     // (chain eliminated inside k_sweep: one workgroup per W W^T tile rides in the gather launch, one for the inverses of the chain's diagonal blocks in the step launch;
     //  a solve on the prechain path reads S' on the visual sub-space + the diagonal only -- vil_linearize, the marginalisation and sharded solves all of it)
     if (!merged) {
         DevP Pg = view(c, 0);
-        const bool po = step && c->P.prechain != 0 && !c->split;
+        const bool po = step && S.prechain != 0 && !c->split;
         Pg.gather_pose_only = po ? 1 : 0;
-        const int ng = po ? c->n_blocks_reduce_po : c->n_blocks_reduce;
-        hipLaunchKernelGGL(k_reduce, dim3(ng + ((step && c->P.prechain == 2) ? c->n_ww : 0)), dim3(VIL_THREADS), 0, c->stream, Pg, ng);
+        const int ng = po ? S.n_reduce_po : S.n_reduce;
+        hipLaunchKernelGGL(k_reduce, dim3(ng + ((step && S.prechain == 2) ? S.n_ww : 0)), dim3(VIL_THREADS), 0, c->stream, Pg, ng);
     }
     if (ev_mid) hipEventRecord(ev_mid, c->stream);
     if (c->split) {                                    // the one collective of the iteration
@@ -1582,12 +1581,8 @@ static int launch_reduce_step(vil_ctx* c, const SolveOpts& so, bool step, hipEve
     DevP Ps = view(c, 1);
     if (!merged) { Ps.rs_merged = 0; Ps.n_ww = 0; Ps.n_gather = 0; }
     Ps.gather_pose_only = merged ? 1 : 0;
-    const dim3 g(1 + c->P.n_help + (merged ? (c->P.prechain ? 1 : 0) + c->n_ww + c->n_gather_m : (c->P.prechain == 2 ? 1 : 0))), b(VIL_STEP_THREADS);      // (prechain 2: + prechain_inverses)
-    if (c->P.chain == 3) hipLaunchKernelGGL((k_step<true, 3>), g, b, c->lds_step, c->stream, Ps, so);
-    else if (c->P.chain == 1) hipLaunchKernelGGL((k_step<true, 1>), g, b, c->lds_step, c->stream, Ps, so);
-    else if (c->P.chain == 2) hipLaunchKernelGGL((k_step<true, 2>), g, b, c->lds_step, c->stream, Ps, so);
-    else if (c->step_lds) hipLaunchKernelGGL((k_step<true, 0>), g, b, c->lds_step, c->stream, Ps, so);
-    else hipLaunchKernelGGL((k_step<false, 0>), g, b, c->lds_step, c->stream, Ps, so);
+    const int g = 1 + c->P.n_help + (merged ? (S.prechain ? 1 : 0) + S.n_ww + S.n_gather_m : (S.prechain == 2 ? 1 : 0));      // (prechain 2: + prechain_inverses)
+    launch_chosen(c, S.step_fn, g, VIL_STEP_THREADS, S.lds_step, Ps, so);
     return VIL_OK;
 }
 
@@ -1670,16 +1665,20 @@ int vil_reset_state(vil_ctx* c) {
     return VIL_OK;
 }
 
-// One attempt at the solve with the launch structure the context holds right now (c->fused: one launch per iteration; else sweep + gather / step launches).
+// The best rung of the ladder of launch structures: 0 the whole solve in one resident launch (k_solve), 1 one launch per iteration (k_iter), 2 sweep + gather / step launches
+static int top_rung(const vil_ctx* c) {
+    return !c->ls.fused || c->split ? 2 : (c->ls.persist && !c->profiling ? 0 : 1);
+}
+// One attempt at the solve on rung `rung` of the ladder (top_rung).
 // *gave_up: a wait inside a launch gave up (status -2 from the master, or no launch ever reported `done`): the caller decides about the retry.
-static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, const std::chrono::steady_clock::time_point t0, const bool direct, bool* gave_up) {
+static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, const std::chrono::steady_clock::time_point t0, const bool direct, const int rung, bool* gave_up) {
     const SolveOpts so = to_dev_opts(o);
     c->mirror_state = false;
     *gave_up = false;
-    const bool persist = c->persist && c->fused && !c->split && !c->profiling;      // (the phase stamps and the per-launch events belong to the one-launch iteration)
+    const bool persist = rung == 0, fused = rung <= 1;
     int st = init_ctl(c, o, 0);
     if (st != VIL_OK) return st;
-    if ((c->profiling || (c->stamps && persist)) && c->fused && c->d_prof) HIPCHK(hipMemsetAsync(c->d_prof, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
+    if ((c->profiling || (c->stamps && persist)) && fused && c->d_prof) HIPCHK(hipMemsetAsync(c->d_prof, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
     // every iteration = sweep + gather + step kernel; `done` turns the tail of a chunk into no-ops, and the first sweep launch that finds
     // the solve finished writes the result out (vil_finish.hpp); k_finish at the end of every chunk covers a solve that ends in its last iteration
     bool finished = false, polled_done = false;
@@ -1690,7 +1689,7 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
     // ~5 us per dead launch and the host nothing, one that is too SHORT costs a host round trip (~70 us) and a second chunk.  The first solve of an upload -- what a
     // tracker runs per image, iteration counts wandering by one or two from image to image -- therefore enqueues the largest count of the last eight solves plus two;
     // re-solves of one upload (graph replay, the same count again and again) keep the exact size.
-    if (c->fused && c->solves_since_upload == 0) { int mx = 3; for (int v : c->recent_live) mx = std::max(mx, v); chunk = std::min(VIL_MAX_CHUNK, mx + 2); }
+    if (fused && c->solves_since_upload == 0) { int mx = 3; for (int v : c->recent_live) mx = std::max(mx, v); chunk = std::min(VIL_MAX_CHUNK, mx + 2); }
     if (c->profiling) chunk = std::min(chunk, (int)c->ev.size() / 2 - 1);      // (events bracket every launch of a chunk: ev[2 q], ev[2 q + 1], ev[2 launched])
     for (int it = 0; it <= o->max_iterations + 8 && !finished; chunk = 3) {
         int launched = 0;
@@ -1710,7 +1709,7 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
                 hipGraph_t graph = nullptr;
                 HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
                 int cst = VIL_OK;
-                for (int q = 0; q < nthis && cst == VIL_OK; ++q) { if (c->fused) cst = launch_iter(c, so); else { launch_sweep(c, so); cst = launch_reduce_step(c, so, true, nullptr); } }
+                for (int q = 0; q < nthis && cst == VIL_OK; ++q) { if (fused) cst = launch_iter(c, so); else { launch_sweep(c, so); cst = launch_reduce_step(c, so, true, nullptr); } }
                 hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);
                 const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
                 const bool forced = c->fail_capture > 0;
@@ -1745,7 +1744,7 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
         if (launched == 0) {
             for (int q = 0; q < chunk && it <= o->max_iterations + 8; ++q, ++it, ++launched) {
                 if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q], c->stream));
-                if (c->fused) {
+                if (fused) {
                     // (one launch: the events bracket the whole iteration; what the sweep roles took inside it comes from the launch's own clock stamps, below)
                     st = launch_iter(c, so);
                     if (st != VIL_OK) return st;
@@ -1788,7 +1787,7 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
             live = std::max(0, std::min(live, launched));
             for (int q = 0; q < live; ++q) {
                 float ms = 0.f;
-                if (c->fused) {      // one launch: the events give its whole duration (to step_ms; the sweep phase's share moves to sweep_ms from the launch's own stamps, below)
+                if (fused) {      // one launch: the events give its whole duration (to step_ms; the sweep phase's share moves to sweep_ms from the launch's own stamps, below)
                     HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q], c->ev[2 * q + 2])); c->prof.step_ms += ms; c->prof.sweep_launches++; c->prof.step_launches++;
                     continue;
                 }
@@ -1815,7 +1814,7 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
     c->solves_since_upload++;
     c->last_live = ctl.n_sweeps;
     c->recent_live[c->recent_at++ & 7] = ctl.n_sweeps;
-    if ((c->profiling || (c->stamps && persist)) && c->fused && c->d_prof && ctl.n_sweeps <= 64) {
+    if ((c->profiling || (c->stamps && persist)) && fused && c->d_prof && ctl.n_sweeps <= 64) {
         // the launches' own clock stamps (100 MHz): the sweep phase of a one-launch iteration = first workgroup started -> last sweep role posted
         std::vector<unsigned long long>& hp = c->last_stamps; hp.assign((size_t)64 * VIL_PROF_SLOTS, 0ull);
         HIPCHK(hipMemcpyAsync(hp.data(), c->d_prof, 8 * hp.size(), hipMemcpyDeviceToHost, c->stream));
@@ -1882,7 +1881,6 @@ int vil_solve_resident(vil_ctx* c, const vil_options* o, vil_summary* sum) {
     // state it started from -- co-residency is a property of the whole device (another process's persistent kernel, a CU mask the occupancy query does not see) and the
     // library's gate is process-local, so this is the way out instead of a hang; the caller (optimization(), estimator.cpp:1400-1414) has no retry of its own.
     // A rung that gives up in two consecutive solves is left out for the next 256 solves of the context (a masked device must not pay the wait per image).
-    const bool cfg_persist = c->persist, cfg_fused = c->fused;
     auto restore = [&]() -> int {
         HIPCHK(hipStreamSynchronize(c->stream));      // the drained launches of the attempt (every wait returns at once behind the abort word)
         hipLaunchKernelGGL(k_state_reset, dim3((c->NS + 255) / 256), dim3(256), 0, c->stream, c->P.x[0], c->P.x[1], (const double*)c->d_xsave, c->NS);
@@ -1890,16 +1888,13 @@ int vil_solve_resident(vil_ctx* c, const vil_options* o, vil_summary* sum) {
         return VIL_OK;
     };
     for (int q = 0; q < 2; ++q) if (c->rung_cooldown[q] > 0) c->rung_cooldown[q]--;
-    const bool can_persist = cfg_persist && cfg_fused && !c->split && !c->profiling && !c->in_batch, can_fused = cfg_fused && !c->split;
-    int first = can_persist && c->rung_cooldown[0] == 0 ? 0 : (can_fused && c->rung_cooldown[1] == 0 ? 1 : 2);
-    if (!can_fused) first = 2;
+    int first = top_rung(c);
+    if (first == 0 && (c->in_batch || c->rung_cooldown[0] > 0)) first = 1;      // (the solves of a batch share the device: never the resident launch)
+    if (first == 1 && c->rung_cooldown[1] > 0) first = 2;
     bool gave_up = false, retried = false;
     int st = VIL_ERR_DEVICE;
     for (int rung = first; rung <= 2; ++rung) {
-        if (rung == 1 && !can_fused) continue;
-        c->persist = rung == 0; c->fused = cfg_fused && rung <= 1;
-        st = solve_attempt(c, o, sum, t0, hook || retried, &gave_up);
-        c->persist = cfg_persist; c->fused = cfg_fused;
+        st = solve_attempt(c, o, sum, t0, hook || retried, rung, &gave_up);
         if (!hook_sticky) { c->P.drop_role = -1; c->P.drop_launch = -1; }
         if (!gave_up) {
             if (rung < 2) c->rung_fail_run[rung] = 0;
@@ -1931,7 +1926,7 @@ int vil_solve_batch(vil_ctx** ctxs, int32_t n, const vil_options* o, vil_summary
     int group = n;
     {
         int waiting = 0, cap = 1 << 30;
-        for (int i = 0; i < n; ++i) { const vil_ctx* c = ctxs[i]; waiting = std::max(waiting, 2 + c->P.n_help + c->n_ww); const int v = c->P.vis_ts == 2 ? 0 : 1; if (c->fused && c->cap_iter[v] > 0) cap = std::min(cap, c->cap_iter[v]); }
+        for (int i = 0; i < n; ++i) { const vil_ctx* c = ctxs[i]; waiting = std::max(waiting, 2 + c->P.n_help + c->ls.n_ww); if (c->ls.fused && c->ls.cap_fused > 0) cap = std::min(cap, c->ls.cap_fused); }
         while (group > 1 && !fits_per_xcd(group * waiting, cap)) --group;
         // ... and at most half of the device may wait: the workgroups the waiting ones wait for need the other half.  How many launches really run at once is the
         // runtime's number of hardware queues (four unless GPU_MAX_HW_QUEUES says otherwise): with eight queues eight windows of configs[1] waited on 208 of 256
@@ -2192,12 +2187,12 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
         const size_t a_bytes = 8 * nn, cap = 156 * 1024;
         if (a_bytes > cap) return VIL_ERR_UNSUPPORTED;
         const size_t dyn = std::max<size_t>(4096, a_bytes);
-        if (dyn > 48 * 1024 && (int)dyn > c->attr_marg[0]) { HIPCHK(hipFuncSetAttribute((const void*)k_marg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); c->attr_marg[0] = (int)dyn; }
+        if (dyn > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_marg, dyn));
         hipLaunchKernelGGL(k_marg, dim3(1), dim3(MARG_THREADS), dyn, c->stream, M, 0);
         if (!VIL_TUNE_ENV("VIL_MARG_PIVOTED")) {               // un-pivoted factorisation on the matrix cores first; pivoted fallback below
             const size_t Tm = (size_t)(n + 1 + 15) / 16, tb = 8 * (size_t)TILE_SZ * (Tm * (Tm + 1) / 2);
             if (tb + sizeof(vd::StepShared) + 512 <= 160 * 1024) {
-                if (tb > 48 * 1024 && (int)tb > c->attr_marg[1]) { HIPCHK(hipFuncSetAttribute((const void*)k_marg_fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb)); c->attr_marg[1] = (int)tb; }
+                if (tb > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_marg_fast, tb));
                 hipLaunchKernelGGL(k_marg_fast, dim3(1), dim3(VIL_STEP_THREADS), tb, c->stream, M);
             }
         }
@@ -2215,7 +2210,7 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
         pc.pJ0 = w.pJ0(dst); pc.pr0 = w.pr0(dst); pc.px0 = w.px0(dst); pc.pH = w.pH(dst); pc.pg0 = w.pg0(dst); pc.pc0 = w.pc0(dst); pc.status = w.d_wstat;
         {
             const size_t pl = 8 * ((size_t)n * (n + 1) + n + 8);
-            if (pl > 48 * 1024 && (int)pl > c->attr_commit) { HIPCHK(hipFuncSetAttribute((const void*)k_prior_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl)); c->attr_commit = (int)pl; }
+            if (pl > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_prior_commit, pl));
             hipLaunchKernelGGL(k_prior_commit, dim3(16), dim3(256), pl, c->stream, pc);
         }
         w.cur = dst; w.pn = n; w.pm = nd + n_lm_elim;
@@ -2423,9 +2418,9 @@ int vil_profile_workgroups(vil_ctx* c, int32_t launch, uint64_t* times, int32_t 
 int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->slim_emul = on != 0; return VIL_OK; }
 int vil_debug_get_launch_structure(vil_ctx* c, int32_t* launches_per_iteration, int32_t* one_launch) {
     if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
-    const bool merged = c->P.rs_merged != 0 && !c->split;
-    if (launches_per_iteration) *launches_per_iteration = (c->fused && !c->split) ? ((c->persist && !c->profiling) ? 0 : 1) : (merged ? 2 : 3);      // 0: the whole solve is one resident launch (k_solve)
-    if (one_launch) *one_launch = (c->fused && !c->split) ? 1 : 0;
+    const int rung = top_rung(c);
+    if (launches_per_iteration) *launches_per_iteration = rung < 2 ? rung : (c->ls.rs_merged != 0 && !c->split ? 2 : 3);      // 0: the whole solve is one resident launch (k_solve)
+    if (one_launch) *one_launch = rung < 2 ? 1 : 0;
     return VIL_OK;
 }
 int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
@@ -2781,7 +2776,7 @@ int vil_win_prior_set(vil_ctx* c, const vil_prior* pr) {
     pc.pJ0 = w.pJ0(dst); pc.pr0 = w.pr0(dst); pc.px0 = w.px0(dst); pc.pH = w.pH(dst); pc.pg0 = w.pg0(dst); pc.pc0 = w.pc0(dst); pc.status = w.d_wstat;
     {
         const size_t pl = 8 * (n * (n + 1) + n + 8);
-        if (pl > 48 * 1024 && (int)pl > c->attr_commit) { HIPCHK(hipFuncSetAttribute((const void*)k_prior_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl)); c->attr_commit = (int)pl; }
+        if (pl > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_prior_commit, pl));
         hipLaunchKernelGGL(k_prior_commit, dim3(16), dim3(256), pl, c->stream, pc);
     }
     HIPCHK(hipStreamSynchronize(c->stream));
