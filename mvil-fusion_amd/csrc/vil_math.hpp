@@ -78,6 +78,11 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// wave64 butterfly minimum of 64-bit keys: every lane ends with it
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
+    for (int o = 32; o; o >>= 1) { const unsigned long long w = __shfl_xor(v, o); v = w < v ? w : v; }
+    return v;
+}
 
 // wave64 sum on the DPP crossbar (no LDS traffic, a few cycles per step instead of a ds_bpermute round trip): rotate-and-add
 // inside each row of 16 lanes, then the two row broadcasts carry the row totals to lane 63, which is read back as a

@@ -25,7 +25,9 @@
 #include <cstring>
 
 #include "../../include/vildepth.h"
+#include "vil_host.hpp"
 #include "vil_knn.hpp"
+#include "vil_math.hpp"
 
 #define VD_BINS VDEPTH_BINS
 #define VD_IMG (VD_BINS * VD_BINS)
@@ -34,7 +36,6 @@
 #define VD_ROW_WAVES (VD_ROW_THREADS / 64)
 #define VD_EMPTY (~0ull)
 #define VD_TAB 368                   // ints reserved for a VD_BINS(+1)-entry table
-#define VDCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (getenv("VIL_DEBUG")) fprintf(stderr, "vildepth.hip:%d: %s\n", __LINE__, hipGetErrorString(e_)); return VIL_ERR_DEVICE; } } while (0)
 
 namespace {
 
@@ -107,11 +108,6 @@ __global__ __launch_bounds__(VD_ROW_THREADS) void k_depth_compact(const float4* 
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
-    for (int o = 32; o; o >>= 1) { const unsigned long long w = __shfl_xor(v, o); v = w < v ? w : v; }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_depth_query(int n_feat, const float* __restrict__ feat, const float4* __restrict__ sphere, const int* __restrict__ rowtab, float thr,
                                                      float* __restrict__ depth, int* __restrict__ nn3, int* __restrict__ hdr) {
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(256) void k_depth_query(int n_feat, const float* __
         unsigned long long best[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {                                                               // a key is unique (its index): one lane pops
-            best[t] = wave_min64(k0);
+            best[t] = vd::wave_min64(k0);
             if (k0 == best[t] && k0 != VD_EMPTY) { k0 = k1; k1 = k2; k2 = VD_EMPTY; }
         }
         if (best[2] != VD_EMPTY && __uint_as_float((unsigned)(best[2] >> 32)) < thr) {             // step 8
@@ -159,85 +155,69 @@ __global__ __launch_bounds__(256) void k_depth_query(int n_feat, const float* __
     }
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
-struct vdepth_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vdepth_ctx : vilhost::Device {        // d_mem: cloud | image | row counters, counters, depths | row table | sphere | matrices, features | nn3
     int max_cloud = 0, max_feat = 0, n_cloud = 0;
     float thr = 0.f;                                        // step 8's threshold
-    char* d_mem = nullptr;                                  // cloud | image | row counters, counters, depths | row table | sphere | matrices, features | nn3
     char* h_cloud = nullptr; char* h_in = nullptr; char* h_out = nullptr;      // pinned: cloud upload, matrices + features, counters + depths
     size_t o_cloud = 0, o_img = 0, o_rowcnt = 0, o_hdr = 0, o_depth = 0, o_rowtab = 0, o_sphere = 0, o_in = 0, o_nn3 = 0;
     int last_sphere = 0, last_feat = 0; bool last_on_device = false;          // what vdepth_debug_read reads
-    bool profiling = false; hipEvent_t ev[VDEPTH_NUM_KERNELS + 1] = {}; long long prof_n[VDEPTH_NUM_KERNELS] = {}; double prof_ms[VDEPTH_NUM_KERNELS] = {};
+    vilhost::Profiler<VDEPTH_NUM_KERNELS, VDEPTH_NUM_KERNELS + 1> prof;
 };
 
 extern "C" {
 
 int vdepth_create(int32_t device, int32_t max_cloud_points, int32_t max_features, vdepth_ctx** out) {
     if (!out || max_cloud_points < 1 || max_features < 1) return VIL_ERR_INVALID_ARGUMENT;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VIL_ERR_DEVICE;      // no CPU fallback
-    VDCHK(hipSetDevice(device));
     vdepth_ctx* c = new vdepth_ctx();
-    c->device = device; c->max_cloud = max_cloud_points; c->max_feat = max_features;
+    c->max_cloud = max_cloud_points; c->max_feat = max_features;
     c->thr = (float)std::pow(std::sin(0.5 / 180.0 * M_PI) * 5.0, 2);
     const size_t N = (size_t)max_cloud_points, F = (size_t)max_features;
-    size_t o = 0;
-    c->o_cloud = o; o += 16 * N;
-    c->o_img = o; o += 8 * (size_t)VD_IMG;
-    c->o_rowcnt = o; o += 4 * VD_TAB;                       // row counters and counters are cleared together,
-    c->o_hdr = o; o += 4 * H_INTS;                          // counters and depths are read back together
-    c->o_depth = o; o += up16(4 * F);
-    c->o_rowtab = o; o += 4 * VD_TAB;
-    c->o_sphere = o; o += 16 * (size_t)VD_IMG;
-    c->o_in = o; o += up16(4 * (24 + 3 * F));
-    c->o_nn3 = o; o += up16(12 * F);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_mem, o) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_cloud, 16 * N, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void**)&c->h_in, up16(4 * (24 + 3 * F)), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_out, 4 * H_INTS + up16(4 * F), hipHostMallocDefault) != hipSuccess) {
-        vdepth_destroy(c);
-        return VIL_ERR_DEVICE;
-    }
+    static_assert((4 * VD_TAB) % 16 == 0 && (4 * H_INTS) % 16 == 0, "the three fields below must lie back to back");
+    vilhost::Arena a;
+    c->o_cloud = a.take(16 * N);
+    c->o_img = a.take(8 * (size_t)VD_IMG);
+    c->o_rowcnt = a.take(4 * VD_TAB);                       // row counters and counters are cleared together,
+    c->o_hdr = a.take(4 * H_INTS);                          // counters and depths are read back together
+    c->o_depth = a.take(4 * F);
+    c->o_rowtab = a.take(4 * VD_TAB);
+    c->o_sphere = a.take(16 * (size_t)VD_IMG);
+    c->o_in = a.take(4 * (24 + 3 * F));
+    c->o_nn3 = a.take(12 * F);
+    hipError_t err = c->open(device, a.bytes);
+    if (err == hipSuccess) err = c->pin(&c->h_cloud, 16 * N);
+    if (err == hipSuccess) err = c->pin(&c->h_in, vilhost::up16(4 * (24 + 3 * F)));
+    if (err == hipSuccess) err = c->pin(&c->h_out, 4 * H_INTS + vilhost::up16(4 * F));
+    if (err != hipSuccess) { vdepth_destroy(c); VILCHK(err); }
     *out = c;
     return VIL_OK;
 }
 
 void vdepth_destroy(vdepth_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipFree(c->d_mem);
-    if (c->h_cloud) hipHostFree(c->h_cloud);
-    if (c->h_in) hipHostFree(c->h_in);
-    if (c->h_out) hipHostFree(c->h_out);
-    for (hipEvent_t e : c->ev) if (e) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 
 int vdepth_profile_enable(vdepth_ctx* c, int32_t enable) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    VDCHK(hipSetDevice(c->device));
-    if (enable && !c->ev[0]) for (hipEvent_t& e : c->ev) VDCHK(hipEventCreate(&e));
-    c->profiling = enable != 0;
+    VILCHK(c->prof.enable(c->device, enable != 0));
     return VIL_OK;
 }
 int vdepth_profile_read(vdepth_ctx* c, int64_t* launches3, double* total_ms3) {
     if (!c || !launches3 || !total_ms3) return VIL_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < VDEPTH_NUM_KERNELS; ++k) { launches3[k] = c->prof_n[k]; total_ms3[k] = c->prof_ms[k]; c->prof_n[k] = 0; c->prof_ms[k] = 0.0; }
+    c->prof.read(launches3, total_ms3);
     return VIL_OK;
 }
 
 int vdepth_set_cloud(vdepth_ctx* c, int32_t n, const float* xyzi) {
     if (!c || n < 0 || n > c->max_cloud || (n && !xyzi)) return VIL_ERR_INVALID_ARGUMENT;
     if (n) {
-        VDCHK(hipSetDevice(c->device));
+        VILCHK(hipSetDevice(c->device));
         memcpy(c->h_cloud, xyzi, 16 * (size_t)n);
-        VDCHK(hipMemcpyAsync(c->d_mem + c->o_cloud, c->h_cloud, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        VDCHK(hipStreamSynchronize(c->stream));
+        VILCHK(hipMemcpyAsync(c->d_mem + c->o_cloud, c->h_cloud, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        VILCHK(hipStreamSynchronize(c->stream));
     }
     c->n_cloud = n;
     return VIL_OK;
@@ -252,7 +232,7 @@ int vdepth_register(vdepth_ctx* c, const float* world_to_lidar, const float* lid
         memset(hdr, 0, 4 * H_INTS);
         for (int i = 0; i < n_feat; ++i) depth_out[i] = -1.0f;
     } else {
-        VDCHK(hipSetDevice(c->device));
+        VILCHK(hipSetDevice(c->device));
         float* in = (float*)c->h_in;
         memcpy(in, world_to_lidar, 48); memcpy(in + 12, lidar_to_view, 48);
         if (n_feat) memcpy(in + 24, feat_xyz, 12 * (size_t)n_feat);
@@ -260,22 +240,21 @@ int vdepth_register(vdepth_ctx* c, const float* world_to_lidar, const float* lid
         const float4* d_cloud = (const float4*)(d + c->o_cloud); unsigned long long* d_img = (unsigned long long*)(d + c->o_img);
         int* d_rowcnt = (int*)(d + c->o_rowcnt); int* d_hdr = (int*)(d + c->o_hdr); int* d_rowtab = (int*)(d + c->o_rowtab);
         float4* d_sphere = (float4*)(d + c->o_sphere); const float* d_in = (const float*)(d + c->o_in);
-        const bool prof = c->profiling;
-        VDCHK(hipMemcpyAsync(d + c->o_in, in, 4 * (24 + 3 * (size_t)n_feat), hipMemcpyHostToDevice, c->stream));
-        VDCHK(hipMemsetAsync(d_img, 0xff, 8 * (size_t)VD_IMG, c->stream));
-        VDCHK(hipMemsetAsync(d_rowcnt, 0, 4 * (VD_TAB + H_INTS), c->stream));
-        if (prof) VDCHK(hipEventRecord(c->ev[0], c->stream));
+        VILCHK(hipMemcpyAsync(d + c->o_in, in, 4 * (24 + 3 * (size_t)n_feat), hipMemcpyHostToDevice, c->stream));
+        VILCHK(hipMemsetAsync(d_img, 0xff, 8 * (size_t)VD_IMG, c->stream));
+        VILCHK(hipMemsetAsync(d_rowcnt, 0, 4 * (VD_TAB + H_INTS), c->stream));
+        VILCHK(c->prof.mark(0, c->stream));
         hipLaunchKernelGGL(k_depth_project, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d_cloud, d_in, d_img, d_rowcnt, d_hdr);
-        if (prof) VDCHK(hipEventRecord(c->ev[1], c->stream));
+        VILCHK(c->prof.mark(1, c->stream));
         hipLaunchKernelGGL(k_depth_compact, dim3(VD_BINS), dim3(VD_ROW_THREADS), 0, c->stream, d_cloud, d_in, d_img, d_rowcnt, d_rowtab, d_sphere, d_hdr);
-        if (prof) VDCHK(hipEventRecord(c->ev[2], c->stream));
+        VILCHK(c->prof.mark(2, c->stream));
         if (n_feat) hipLaunchKernelGGL(k_depth_query, dim3((n_feat + 3) / 4), dim3(256), 0, c->stream, n_feat, d_in + 24, d_sphere, d_rowtab, c->thr, (float*)(d + c->o_depth),
                                        (int*)(d + c->o_nn3), d_hdr);
-        if (prof) VDCHK(hipEventRecord(c->ev[3], c->stream));
-        VDCHK(hipMemcpyAsync(c->h_out, d_hdr, 4 * H_INTS + 4 * (size_t)n_feat, hipMemcpyDeviceToHost, c->stream));
-        VDCHK(hipStreamSynchronize(c->stream));
-        VDCHK(hipGetLastError());
-        if (prof) for (int k = 0; k < (n_feat ? 3 : 2); ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess) { c->prof_ms[k] += ms; c->prof_n[k]++; } }
+        VILCHK(c->prof.mark(3, c->stream));
+        VILCHK(hipMemcpyAsync(c->h_out, d_hdr, 4 * H_INTS + 4 * (size_t)n_feat, hipMemcpyDeviceToHost, c->stream));
+        VILCHK(hipStreamSynchronize(c->stream));
+        VILCHK(hipGetLastError());
+        for (int k = 0; k < (n_feat ? 3 : 2); ++k) c->prof.span(k, k, k + 1);                       // no features: k_depth_query was not launched
         if (n_feat) memcpy(depth_out, c->h_out + 4 * H_INTS, 4 * (size_t)n_feat);
         c->last_sphere = hdr[H_NSPHERE]; c->last_on_device = true;
     }
@@ -289,10 +268,10 @@ int vdepth_debug_read(vdepth_ctx* c, float* sphere_xyzr, int32_t capacity, int32
         if (nn3) for (int i = 0; i < 3 * c->last_feat; ++i) nn3[i] = -1;
         return VIL_OK;
     }
-    VDCHK(hipSetDevice(c->device));
-    if (sphere_xyzr && c->last_sphere) VDCHK(hipMemcpyAsync(sphere_xyzr, c->d_mem + c->o_sphere, 16 * (size_t)c->last_sphere, hipMemcpyDeviceToHost, c->stream));
-    if (nn3 && c->last_feat) VDCHK(hipMemcpyAsync(nn3, c->d_mem + c->o_nn3, 12 * (size_t)c->last_feat, hipMemcpyDeviceToHost, c->stream));
-    VDCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipSetDevice(c->device));
+    if (sphere_xyzr && c->last_sphere) VILCHK(hipMemcpyAsync(sphere_xyzr, c->d_mem + c->o_sphere, 16 * (size_t)c->last_sphere, hipMemcpyDeviceToHost, c->stream));
+    if (nn3 && c->last_feat) VILCHK(hipMemcpyAsync(nn3, c->d_mem + c->o_nn3, 12 * (size_t)c->last_feat, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
     return VIL_OK;
 }
 

@@ -19,15 +19,12 @@
 
 #include "../../include/vilmap.h"
 #include "vil_internal.h"
+#include "vil_host.hpp"
 #include "vil_coop.hpp"
 #include "vil_knn.hpp"
 #include "vil_pose1.hpp"
 
-#define VM_OK 0
-#define VM_ERR_INVALID -1
-#define VM_ERR_DEVICE -2
 #define VM_THREADS 256
-#define VMCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (getenv("VIL_DEBUG")) fprintf(stderr, "vilmap.hip:%d: %s\n", __LINE__, hipGetErrorString(e_)); return VM_ERR_DEVICE; } } while (0)
 
 namespace {
 using namespace vknn;
@@ -249,9 +246,7 @@ void quat_to_R(const double* q, double* R) {
 
 }  // namespace
 
-struct vmap_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vmap_ctx : vilhost::Device {                  // its buffers grow on demand: no arena
     int nc = 0, ns = 0;
     float* d_cmap = nullptr; float* d_smap = nullptr; size_t cmap_cap = 0, smap_cap = 0;
     vknn::GridBuild gc, gs;
@@ -266,7 +261,7 @@ struct vmap_ctx {
     char* h_res = nullptr; void* d_res = nullptr;     // pinned + mapped: the second round's Pose1Out | sequence word, written by k_pose_solve, polled by the host
     int coop_cap = -1;                                 // workgroups of k_pose_solve the device holds at once (vil_coop.hpp)
     int fused_max = 1 << 20;                           // scans up to this many points take the one-launch pose solve (vmap_set_fused_max; 0 = always the window solver)
-    bool profiling = false; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; long long prof_n[2] = {0, 0}; double prof_ms[2] = {0.0, 0.0};
+    vilhost::Profiler<2, 4> prof;                      // k_map_search, k_map_fit
 };
 
 namespace {
@@ -274,15 +269,15 @@ namespace {
 int upload_scan(vmap_ctx* c, int n_corner, const float* corner, int n_surf, const float* surf) {
     const int nq = n_corner + n_surf;
     const size_t need_scan = 16 * (size_t)nq + 16, need_work = (size_t)nq * (40 + 4 + 80 + 40) + 8 * ((size_t)nq / VM_THREADS + 1) + 256;
-    if (need_scan > c->scan_cap) { hipFree(c->d_scan); c->d_scan = nullptr; c->scan_cap = 0; VMCHK(hipMalloc(&c->d_scan, 2 * need_scan)); c->scan_cap = 2 * need_scan; }
-    if (need_work > c->work_cap) { hipFree(c->d_work); c->d_work = nullptr; c->work_cap = 0; VMCHK(hipMalloc(&c->d_work, 2 * need_work)); c->work_cap = 2 * need_work; }
+    if (need_scan > c->scan_cap) { hipFree(c->d_scan); c->d_scan = nullptr; c->scan_cap = 0; VILCHK(hipMalloc(&c->d_scan, 2 * need_scan)); c->scan_cap = 2 * need_scan; }
+    if (need_work > c->work_cap) { hipFree(c->d_work); c->d_work = nullptr; c->work_cap = 0; VILCHK(hipMalloc(&c->d_work, 2 * need_work)); c->work_cap = 2 * need_work; }
     // through a pinned image: one DMA instead of two staged pageable copies (every entry point ends with a stream
     // synchronisation, so the image is free again when the next call starts)
-    if (need_scan > c->h_scan_cap) { if (c->h_scan) hipHostFree(c->h_scan); c->h_scan = nullptr; c->h_scan_cap = 0; VMCHK(hipHostMalloc((void**)&c->h_scan, 2 * need_scan, hipHostMallocDefault)); c->h_scan_cap = 2 * need_scan; }
+    if (need_scan > c->h_scan_cap) { if (c->h_scan) hipHostFree(c->h_scan); c->h_scan = nullptr; c->h_scan_cap = 0; VILCHK(hipHostMalloc((void**)&c->h_scan, 2 * need_scan, hipHostMallocDefault)); c->h_scan_cap = 2 * need_scan; }
     if (n_corner) memcpy(c->h_scan, corner, 16 * (size_t)n_corner);
     if (n_surf) memcpy(c->h_scan + 4 * (size_t)n_corner, surf, 16 * (size_t)n_surf);
-    if (nq) VMCHK(hipMemcpyAsync(c->d_scan, c->h_scan, 16 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
-    return VM_OK;
+    if (nq) VILCHK(hipMemcpyAsync(c->d_scan, c->h_scan, 16 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
+    return VIL_OK;
 }
 // association of the uploaded scan at pose (q, t); compacted on the host in scan order
 int associate_uploaded(vmap_ctx* c, int n_corner, int n_surf, const double* q, const double* t, int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
@@ -290,27 +285,27 @@ int associate_uploaded(vmap_ctx* c, int n_corner, int n_surf, const double* q, c
     *n_edge = 0; *n_plane = 0;
     const int nqc = c->nc ? n_corner : 0, nqs = c->ns ? n_surf : 0;       // an empty map yields no factors of that class
     const int nq = n_corner + n_surf;
-    if (nq == 0 || nqc + nqs == 0) return VM_OK;
+    if (nq == 0 || nqc + nqs == 0) return VIL_OK;
     // queries are addressed in the uploaded layout (corner block, then surf block); a class without a map is skipped by nmap < k
     double* d_slot = (double*)c->d_work; int* d_nn = (int*)(c->d_work + 80 * (size_t)nq); float* d_nd5 = (float*)(d_nn + 10 * (size_t)nq); float* d_nint = d_nd5 + nq; int* d_blk = (int*)(c->d_work + (((size_t)164 * nq + 7) & ~(size_t)7));
-    if (c->profiling) hipEventRecord(c->ev[0], c->stream);
+    VILCHK(c->prof.mark(0, c->stream));
     hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, (const PoseD*)nullptr, c->nc, c->gc.G, c->gc.order, c->gc.cxyz,
                        c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
-    if (c->profiling) { hipEventRecord(c->ev[1], c->stream); hipEventRecord(c->ev[2], c->stream); }
+    VILCHK(c->prof.mark(1, c->stream)); VILCHK(c->prof.mark(2, c->stream));
     hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
-    if (c->profiling) hipEventRecord(c->ev[3], c->stream);
+    VILCHK(c->prof.mark(3, c->stream));
     if (10 * (size_t)nq > c->h_slot_cap) {
         if (c->h_slot) hipHostFree(c->h_slot);
         c->h_slot = nullptr; c->h_slot_cap = 0;
-        VMCHK(hipHostMalloc((void**)&c->h_slot, 8 * 20 * (size_t)nq, hipHostMallocDefault)); c->h_slot_cap = 20 * (size_t)nq;
+        VILCHK(hipHostMalloc((void**)&c->h_slot, 8 * 20 * (size_t)nq, hipHostMallocDefault)); c->h_slot_cap = 20 * (size_t)nq;
     }
-    VMCHK(hipMemcpyAsync(c->h_slot, d_slot, 80 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    VMCHK(hipStreamSynchronize(c->stream));
-    if (c->profiling) for (int k = 0; k < 2; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev[2 * k], c->ev[2 * k + 1]) == hipSuccess) { c->prof_ms[k] += ms; c->prof_n[k]++; } }
+    VILCHK(hipMemcpyAsync(c->h_slot, d_slot, 80 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
+    c->prof.span(0, 0, 1); c->prof.span(1, 2, 3);
     for (int i = 0; i < n_corner; ++i) if (c->h_slot[10 * (size_t)i] != 0.0) { memcpy(edge9 + 9 * (size_t)(*n_edge), &c->h_slot[10 * (size_t)i + 1], 72); ++*n_edge; }
     for (int i = n_corner; i < nq; ++i) if (c->h_slot[10 * (size_t)i] != 0.0) { memcpy(plane7 + 7 * (size_t)(*n_plane), &c->h_slot[10 * (size_t)i + 1], 56); ++*n_plane; }
-    VMCHK(hipGetLastError());
-    return VM_OK;
+    VILCHK(hipGetLastError());
+    return VIL_OK;
 }
 // association of the uploaded scan with the factor tables left ON THE DEVICE in the solver's layout; only the two counts come back
 int associate_device(vmap_ctx* c, int n_corner, int n_surf, const double* q, const double* t, int32_t* n_edge, int32_t* n_plane, vil_device_lidar* dl) {
@@ -319,20 +314,20 @@ int associate_device(vmap_ctx* c, int n_corner, int n_surf, const double* q, con
     const int nq = n_corner + n_surf;
     const int es = (std::max(n_corner, 1) + 31) & ~31, ps = (std::max(n_surf, 1) + 31) & ~31;
     const size_t need = 8 * ((size_t)9 * es + (size_t)7 * ps);
-    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VMCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
-    if (!c->d_cnt) { VMCHK(hipMalloc(&c->d_cnt, 16)); VMCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
+    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VILCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
+    if (!c->d_cnt) { VILCHK(hipMalloc(&c->d_cnt, 16)); VILCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
     dl->edge_soa = c->d_soa; dl->edge_stride = es; dl->plane_soa = c->d_soa + (size_t)9 * es; dl->plane_stride = ps;
-    if (nq == 0) return VM_OK;
+    if (nq == 0) return VIL_OK;
     double* d_slot = (double*)c->d_work; int* d_nn = (int*)(c->d_work + 80 * (size_t)nq); float* d_nd5 = (float*)(d_nn + 10 * (size_t)nq); float* d_nint = d_nd5 + nq; int* d_blk = (int*)(c->d_work + (((size_t)164 * nq + 7) & ~(size_t)7));
     hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, (const PoseD*)nullptr, c->nc, c->gc.G, c->gc.order, c->gc.cxyz,
                        c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
     hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
     hipLaunchKernelGGL(k_map_compact, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, d_slot, d_blk, c->d_soa, es, c->d_soa + (size_t)9 * es, ps, c->d_cnt);
-    VMCHK(hipMemcpyAsync(c->h_cnt, c->d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-    VMCHK(hipStreamSynchronize(c->stream));
-    VMCHK(hipGetLastError());
+    VILCHK(hipMemcpyAsync(c->h_cnt, c->d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipGetLastError());
     *n_edge = c->h_cnt[0]; *n_plane = c->h_cnt[1];
-    return VM_OK;
+    return VIL_OK;
 }
 
 // The whole registration in one submission: both rounds of {search, fit, compact, one-launch pose solve} are enqueued back
@@ -347,10 +342,10 @@ int align_fused(vmap_ctx* c, int n_corner, int n_surf, double* q, double* t, con
     const int nq = n_corner + n_surf;
     const int es = (std::max(n_corner, 1) + 31) & ~31, ps = (std::max(n_surf, 1) + 31) & ~31;
     const size_t need = 8 * ((size_t)9 * es + (size_t)7 * ps);
-    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VMCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
-    if (!c->d_cnt) { VMCHK(hipMalloc(&c->d_cnt, 16)); VMCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
-    if (!c->d_reg) { VMCHK(hipMalloc(&c->d_reg, REG_BYTES)); VMCHK(hipHostMalloc((void**)&c->h_reg, REG_BYTES, hipHostMallocDefault)); }
-    if (!c->d_coop) { VMCHK(hipMalloc(&c->d_coop, sizeof(vp1::Pose1Coop))); VMCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }
+    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VILCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
+    if (!c->d_cnt) { VILCHK(hipMalloc(&c->d_cnt, 16)); VILCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
+    if (!c->d_reg) { VILCHK(hipMalloc(&c->d_reg, REG_BYTES)); VILCHK(hipHostMalloc((void**)&c->h_reg, REG_BYTES, hipHostMallocDefault)); }
+    if (!c->d_coop) { VILCHK(hipMalloc(&c->d_coop, sizeof(vp1::Pose1Coop))); VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }
     if (!c->h_res && !getenv("VIL_NO_POLL")) {
         if (hipHostMalloc((void**)&c->h_res, sizeof(vp1::Pose1Out) + 64, hipHostMallocMapped) == hipSuccess) {
             memset(c->h_res, 0, sizeof(vp1::Pose1Out) + 64);
@@ -373,23 +368,23 @@ int align_fused(vmap_ctx* c, int n_corner, int n_surf, double* q, double* t, con
     vp1::Pose1Out* d_out = (vp1::Pose1Out*)(c->d_reg + REG_OUT);
     for (int round = 0; round < 2; ++round) {
         if (nq > 0) {
-            if (c->profiling && round == 0) VMCHK(hipEventRecord(c->ev[0], c->stream));
+            if (round == 0) VILCHK(c->prof.mark(0, c->stream));
             hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, round ? (const PoseD*)(c->d_reg + REG_RT) : (const PoseD*)nullptr,
                                c->nc, c->gc.G, c->gc.order, c->gc.cxyz, c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
-            if (c->profiling && round == 0) VMCHK(hipEventRecord(c->ev[1], c->stream));
+            if (round == 0) VILCHK(c->prof.mark(1, c->stream));
             hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
-            if (c->profiling && round == 0) VMCHK(hipEventRecord(c->ev[2], c->stream));
+            if (round == 0) VILCHK(c->prof.mark(2, c->stream));
             hipLaunchKernelGGL(k_map_compact, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, d_slot, d_blk, edge_soa, es, plane_soa, ps, c->d_cnt);
-        } else VMCHK(hipMemsetAsync(c->d_cnt, 0, 8, c->stream));
+        } else VILCHK(hipMemsetAsync(c->d_cnt, 0, 8, c->stream));
         hipLaunchKernelGGL(vp1::k_pose_solve, dim3(G), dim3(VP1_THREADS), 0, c->stream, c->d_cnt, edge_soa, es, plane_soa, ps, (double*)(c->d_reg + REG_POSE), (PoseD*)(c->d_reg + REG_RT), *opts,
                            round ? d_out : (const vp1::Pose1Out*)nullptr, d_out + round, c->d_coop, c->reg_epoch, round ? pin1 : pin0,
                            (round && c->d_res) ? (vp1::Pose1Out*)c->d_res : (vp1::Pose1Out*)nullptr, (round && c->d_res) ? (int*)((char*)c->d_res + sizeof(vp1::Pose1Out)) : (int*)nullptr);
         if (round) seq_expect = c->reg_epoch + 1;
         c->reg_epoch += std::min(std::max(opts->max_iterations, 0), VP1_MAX_ITER) + 8;     // one epoch per evaluation: at most max_iterations + 1
-        if (c->reg_epoch > (1 << 30)) { c->reg_epoch = 0; VMCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }   // flags are compared by order: start over from zeroed flags
+        if (c->reg_epoch > (1 << 30)) { c->reg_epoch = 0; VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }   // flags are compared by order: start over from zeroed flags
     }
     bool polled = false;
-    if (hseq && !c->profiling) {                         // the second solve's last act is the record + its sequence word in pinned memory
+    if (hseq && !c->prof.on) {                         // the second solve's last act is the record + its sequence word in pinned memory
         const auto tp0 = std::chrono::steady_clock::now();
         for (long spin = 1;; ++spin) {
             if (*hseq == seq_expect) { polled = true; break; }
@@ -398,94 +393,84 @@ int align_fused(vmap_ctx* c, int n_corner, int n_surf, double* q, double* t, con
         if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_reg + REG_OUT + sizeof(vp1::Pose1Out), c->h_res, sizeof(vp1::Pose1Out)); }
     }
     if (!polled) {
-        VMCHK(hipMemcpyAsync(c->h_reg + REG_OUT, d_out, 2 * sizeof(vp1::Pose1Out), hipMemcpyDeviceToHost, c->stream));
-        VMCHK(hipStreamSynchronize(c->stream));
+        VILCHK(hipMemcpyAsync(c->h_reg + REG_OUT, d_out, 2 * sizeof(vp1::Pose1Out), hipMemcpyDeviceToHost, c->stream));
+        VILCHK(hipStreamSynchronize(c->stream));
     }
-    VMCHK(hipGetLastError());
-    if (c->profiling && nq > 0) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) { c->prof_ms[0] += ms; c->prof_n[0]++; }
-        if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) { c->prof_ms[1] += ms; c->prof_n[1]++; }
-    }
+    VILCHK(hipGetLastError());
+    if (nq > 0) { c->prof.span(0, 0, 1); c->prof.span(1, 1, 2); }
     const vp1::Pose1Out* r = (const vp1::Pose1Out*)(c->h_reg + REG_OUT);
     if (r[1].status != 0) return r[1].status;
     t[0] = r[1].pose[0]; t[1] = r[1].pose[1]; t[2] = r[1].pose[2]; q[0] = r[1].pose[3]; q[1] = r[1].pose[4]; q[2] = r[1].pose[5]; q[3] = r[1].pose[6];
     out->rounds = 2; out->n_edge = r[1].n_edge; out->n_plane = r[1].n_plane; out->iterations = r[1].iterations; out->initial_cost = r[1].initial_cost; out->final_cost = r[1].final_cost;
     out->t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // one submission: association and solve are not separable on the host clock
-    return VM_OK;
+    return VIL_OK;
 }
 }  // namespace
 
 extern "C" {
 
 int vmap_create(int32_t device, vmap_ctx** out) {
-    if (!out) return VM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VM_ERR_DEVICE;      // no CPU fallback
-    VMCHK(hipSetDevice(device));
+    if (!out) return VIL_ERR_INVALID_ARGUMENT;
     vmap_ctx* c = new vmap_ctx();
-    c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VM_ERR_DEVICE; }
+    const hipError_t err = c->open(device, 0);
+    if (err != hipSuccess) { delete c; VILCHK(err); }                    // without an arena a failed open() holds nothing
     *out = c;
-    return VM_OK;
+    return VIL_OK;
 }
 void vmap_destroy(vmap_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipFree(c->d_cmap); hipFree(c->d_smap); hipFree(c->gc.ws); hipFree(c->gs.ws); hipFree(c->d_scan); hipFree(c->d_work); if (c->h_slot) hipHostFree(c->h_slot); hipFree(c->d_soa); hipFree(c->d_cnt); if (c->h_cnt) hipHostFree(c->h_cnt); hipFree(c->d_reg); if (c->h_reg) hipHostFree(c->h_reg); if (c->h_res) hipHostFree(c->h_res); hipFree(c->d_coop); if (c->h_scan) hipHostFree(c->h_scan);
-    for (hipEvent_t e : c->ev) if (e) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 
 int vmap_set_map(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const float* surf) {
-    if (!c || nc < 0 || ns < 0 || (nc && !corner) || (ns && !surf)) return VM_ERR_INVALID;
-    VMCHK(hipSetDevice(c->device));
+    if (!c || nc < 0 || ns < 0 || (nc && !corner) || (ns && !surf)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     c->nc = 0; c->ns = 0;
-    if (16 * (size_t)nc > c->cmap_cap) { hipFree(c->d_cmap); c->d_cmap = nullptr; c->cmap_cap = 0; VMCHK(hipMalloc(&c->d_cmap, 24 * (size_t)nc)); c->cmap_cap = 24 * (size_t)nc; }
-    if (16 * (size_t)ns > c->smap_cap) { hipFree(c->d_smap); c->d_smap = nullptr; c->smap_cap = 0; VMCHK(hipMalloc(&c->d_smap, 24 * (size_t)ns)); c->smap_cap = 24 * (size_t)ns; }
-    if (nc) VMCHK(hipMemcpyAsync(c->d_cmap, corner, 16 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
-    if (ns) VMCHK(hipMemcpyAsync(c->d_smap, surf, 16 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
-    if (nc) VMCHK(vknn::grid_build_adaptive(c->gc, nc, c->d_cmap, 4, c->hc, VM_OCC, c->stream));
-    if (ns) VMCHK(vknn::grid_build_adaptive(c->gs, ns, c->d_smap, 4, c->hs, VM_OCC, c->stream));
-    VMCHK(hipStreamSynchronize(c->stream));
+    if (16 * (size_t)nc > c->cmap_cap) { hipFree(c->d_cmap); c->d_cmap = nullptr; c->cmap_cap = 0; VILCHK(hipMalloc(&c->d_cmap, 24 * (size_t)nc)); c->cmap_cap = 24 * (size_t)nc; }
+    if (16 * (size_t)ns > c->smap_cap) { hipFree(c->d_smap); c->d_smap = nullptr; c->smap_cap = 0; VILCHK(hipMalloc(&c->d_smap, 24 * (size_t)ns)); c->smap_cap = 24 * (size_t)ns; }
+    if (nc) VILCHK(hipMemcpyAsync(c->d_cmap, corner, 16 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
+    if (ns) VILCHK(hipMemcpyAsync(c->d_smap, surf, 16 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
+    if (nc) VILCHK(vknn::grid_build_adaptive(c->gc, nc, c->d_cmap, 4, c->hc, VM_OCC, c->stream));
+    if (ns) VILCHK(vknn::grid_build_adaptive(c->gs, ns, c->d_smap, 4, c->hs, VM_OCC, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
     c->nc = nc; c->ns = ns;
-    return VM_OK;
+    return VIL_OK;
 }
 
 int vmap_associate(vmap_ctx* c, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf, const double* q, const double* t,
                    int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
-    if (!c || !q || !t || !n_edge || !n_plane || n_corner < 0 || n_surf < 0 || (n_corner && (!corner || !edge9)) || (n_surf && (!surf || !plane7))) return VM_ERR_INVALID;
-    VMCHK(hipSetDevice(c->device));
+    if (!c || !q || !t || !n_edge || !n_plane || n_corner < 0 || n_surf < 0 || (n_corner && (!corner || !edge9)) || (n_surf && (!surf || !plane7))) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     const int st = upload_scan(c, n_corner, corner, n_surf, surf);
-    if (st != VM_OK) return st;
+    if (st != VIL_OK) return st;
     return associate_uploaded(c, n_corner, n_surf, q, t, n_edge, edge9, n_plane, plane7);
 }
 
-int vmap_set_fused_max(vmap_ctx* c, int32_t max_points) { if (!c || max_points < 0) return VM_ERR_INVALID; c->fused_max = max_points; return VM_OK; }
+int vmap_set_fused_max(vmap_ctx* c, int32_t max_points) { if (!c || max_points < 0) return VIL_ERR_INVALID_ARGUMENT; c->fused_max = max_points; return VIL_OK; }
 
 int vmap_profile_enable(vmap_ctx* c, int32_t enable) {
-    if (!c) return VM_ERR_INVALID;
-    VMCHK(hipSetDevice(c->device));
-    if (enable && !c->ev[0]) for (hipEvent_t& e : c->ev) VMCHK(hipEventCreate(&e));
-    c->profiling = enable != 0;
-    return VM_OK;
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(c->prof.enable(c->device, enable != 0));
+    return VIL_OK;
 }
 int vmap_profile_read(vmap_ctx* c, int64_t* launches2, double* total_ms2) {
-    if (!c || !launches2 || !total_ms2) return VM_ERR_INVALID;
-    for (int k = 0; k < 2; ++k) { launches2[k] = c->prof_n[k]; total_ms2[k] = c->prof_ms[k]; c->prof_n[k] = 0; c->prof_ms[k] = 0.0; }
-    return VM_OK;
+    if (!c || !launches2 || !total_ms2) return VIL_ERR_INVALID_ARGUMENT;
+    c->prof.read(launches2, total_ms2);
+    return VIL_OK;
 }
 
 int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf,
                double* q, double* t, const vil_options* opts, vmap_summary* out) {
-    if (!c || !solver || !q || !t || !opts || !out) return VM_ERR_INVALID;
+    if (!c || !solver || !q || !t || !opts || !out) return VIL_ERR_INVALID_ARGUMENT;
     memset(out, 0, sizeof *out);
-    if (!(c->nc > 10 && c->ns > 50)) return VM_OK;                      // localMapping.cpp:586 "corner and surf num are not enough"
-    if (n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf)) return VM_ERR_INVALID;
-    VMCHK(hipSetDevice(c->device));
+    if (!(c->nc > 10 && c->ns > 50)) return VIL_OK;                      // localMapping.cpp:586 "corner and surf num are not enough"
+    if (n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     int st = upload_scan(c, n_corner, corner, n_surf, surf);             // the scan is uploaded once for both rounds
-    if (st != VM_OK) return st;
+    if (st != VIL_OK) return st;
     if (c->coop_cap < 0) c->coop_cap = vilcoop::capacity((const void*)vp1::k_pose_solve, VP1_THREADS, 0, c->device);
     if (n_corner + n_surf <= c->fused_max && c->coop_cap >= 1) return align_fused(c, n_corner, n_surf, q, t, opts, out);
     for (int round = 0; round < 2; ++round) {
@@ -493,7 +478,7 @@ int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corn
         const auto ta = std::chrono::steady_clock::now();
         vil_device_lidar dl;
         st = associate_device(c, n_corner, n_surf, q, t, &ne, &np, &dl);   // the factor tables stay on the device, in the solver's layout
-        if (st != VM_OK) return st;
+        if (st != VIL_OK) return st;
         out->t_associate_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
         // one-pose window: pose free, everything else constant, identity LiDAR extrinsic, only the point factors
         vil_problem p; memset(&p, 0, sizeof p);
@@ -511,7 +496,7 @@ int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corn
         out->t_prepare_ms += sum.t_prepare_ms; out->t_solve_ms += sum.t_solve_ms + sum.t_readback_ms;
         out->rounds = round + 1; out->n_edge = ne; out->n_plane = np; out->iterations = sum.iterations; out->initial_cost = sum.initial_cost; out->final_cost = sum.final_cost;
     }
-    return VM_OK;
+    return VIL_OK;
 }
 
 }  // extern "C"

@@ -15,12 +15,9 @@
 #include <vector>
 
 #include "../../include/vilpreint.h"
+#include "vil_host.hpp"
 #include "vil_tuning.hpp"
 
-#define VP_OK 0
-#define VP_ERR_INVALID -1
-#define VP_ERR_DEVICE -2
-#define VPCHK(x) do { if ((x) != hipSuccess) return VP_ERR_DEVICE; } while (0)
 #define PRE_B 24      // samples per batch: an inter-keyframe interval at 200 Hz / 10 Hz (20 samples) is ONE batch; 24 x 720 doubles = 138 kB of LDS
 #define PRE_THREADS 256
 
@@ -316,45 +313,39 @@ void vpre_launch_slot(hipStream_t stream, int ns, const double* dt, const double
     hipLaunchKernelGGL(k_preint, dim3(1), dim3(PRE_THREADS), 0, stream, A);
 }
 
-struct vpre_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vpre_ctx : vilhost::Device {                  // both buffers grow on demand: no arena
     char* d_buf = nullptr; size_t cap = 0;
     char* h = nullptr; size_t hcap = 0;              // pinned staging: one H2D in, one D2H back
-    bool profiling = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; long long prof_n = 0; double prof_ms = 0.0;
+    vilhost::Profiler<1, 2> prof;                      // k_preint
 };
 
 extern "C" {
 
 int vpre_create(int32_t device, vpre_ctx** out) {
-    if (!out) return VP_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VP_ERR_DEVICE;      // no CPU fallback
-    VPCHK(hipSetDevice(device));
+    if (!out) return VIL_ERR_INVALID_ARGUMENT;
     vpre_ctx* c = new vpre_ctx();
-    c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VP_ERR_DEVICE; }
+    const hipError_t err = c->open(device, 0);
+    if (err != hipSuccess) { delete c; VILCHK(err); }                    // without an arena a failed open() holds nothing
     *out = c;
-    return VP_OK;
+    return VIL_OK;
 }
 void vpre_destroy(vpre_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     hipFree(c->d_buf); if (c->h) hipHostFree(c->h);
-    if (c->ev0) { hipEventDestroy(c->ev0); hipEventDestroy(c->ev1); }
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 
 int vpre_integrate(vpre_ctx* c, int32_t n, const int32_t* start, const double* dt, const double* acc, const double* gyr, const double* acc0, const double* gyr0,
                    const double* ba, const double* bg, const double* noise4, double* imu_const, double* jacobian) {
-    if (!c || n < 0 || !start || !acc0 || !gyr0 || !ba || !bg || !noise4 || !imu_const) return VP_ERR_INVALID;
-    if (n == 0) return VP_OK;
-    for (int k = 0; k < n; ++k) if (start[k + 1] < start[k]) return VP_ERR_INVALID;
-    if (start[0] != 0) return VP_ERR_INVALID;
+    if (!c || n < 0 || !start || !acc0 || !gyr0 || !ba || !bg || !noise4 || !imu_const) return VIL_ERR_INVALID_ARGUMENT;
+    if (n == 0) return VIL_OK;
+    for (int k = 0; k < n; ++k) if (start[k + 1] < start[k]) return VIL_ERR_INVALID_ARGUMENT;
+    if (start[0] != 0) return VIL_ERR_INVALID_ARGUMENT;
     const size_t ns = (size_t)start[n];
-    if (ns && (!dt || !acc || !gyr)) return VP_ERR_INVALID;
-    VPCHK(hipSetDevice(c->device));
+    if (ns && (!dt || !acc || !gyr)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     static const bool timing = VIL_TUNE_ENV("VPRE_TIMING") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -362,45 +353,43 @@ int vpre_integrate(vpre_ctx* c, int32_t n, const int32_t* start, const double* d
     // one staging buffer: [start | dt | acc | gyr | acc0 | gyr0 | ba | bg] in, [out | jac] back
     const size_t o_start = 0, o_dt = (4 * (size_t)(n + 1) + 7) & ~(size_t)7, o_acc = o_dt + 8 * ns, o_gyr = o_acc + 24 * ns, o_a0 = o_gyr + 24 * ns, o_g0 = o_a0 + 24 * (size_t)n,
                  o_ba = o_g0 + 24 * (size_t)n, o_bg = o_ba + 24 * (size_t)n, in_bytes = o_bg + 24 * (size_t)n, o_out = in_bytes, o_jac = o_out + 8 * 287 * (size_t)n, total = o_jac + 8 * 225 * (size_t)n;
-    if (total > c->cap) { hipFree(c->d_buf); c->d_buf = nullptr; c->cap = 0; VPCHK(hipMalloc(&c->d_buf, 2 * total)); c->cap = 2 * total; }
-    if (total > c->hcap) { if (c->h) hipHostFree(c->h); c->h = nullptr; c->hcap = 0; VPCHK(hipHostMalloc((void**)&c->h, 2 * total, hipHostMallocDefault)); c->hcap = 2 * total; }
+    if (total > c->cap) { hipFree(c->d_buf); c->d_buf = nullptr; c->cap = 0; VILCHK(hipMalloc(&c->d_buf, 2 * total)); c->cap = 2 * total; }
+    if (total > c->hcap) { if (c->h) hipHostFree(c->h); c->h = nullptr; c->hcap = 0; VILCHK(hipHostMalloc((void**)&c->h, 2 * total, hipHostMallocDefault)); c->hcap = 2 * total; }
     memcpy(c->h + o_start, start, 4 * (size_t)(n + 1));
     if (ns) { memcpy(c->h + o_dt, dt, 8 * ns); memcpy(c->h + o_acc, acc, 24 * ns); memcpy(c->h + o_gyr, gyr, 24 * ns); }
     memcpy(c->h + o_a0, acc0, 24 * (size_t)n); memcpy(c->h + o_g0, gyr0, 24 * (size_t)n); memcpy(c->h + o_ba, ba, 24 * (size_t)n); memcpy(c->h + o_bg, bg, 24 * (size_t)n);
     const auto t1 = now();
-    VPCHK(hipMemcpyAsync(c->d_buf, c->h, in_bytes, hipMemcpyHostToDevice, c->stream));
+    VILCHK(hipMemcpyAsync(c->d_buf, c->h, in_bytes, hipMemcpyHostToDevice, c->stream));
     const auto t2 = now();
     PreArgs A;
     A.n = n; A.start = (const int*)(c->d_buf + o_start); A.dt = (const double*)(c->d_buf + o_dt); A.acc = (const double*)(c->d_buf + o_acc); A.gyr = (const double*)(c->d_buf + o_gyr);
     A.acc0 = (const double*)(c->d_buf + o_a0); A.gyr0 = (const double*)(c->d_buf + o_g0); A.ba = (const double*)(c->d_buf + o_ba); A.bg = (const double*)(c->d_buf + o_bg);
     for (int q = 0; q < 4; ++q) A.nz[q] = noise4[q];
     A.out = (double*)(c->d_buf + o_out); A.jac = jacobian ? (double*)(c->d_buf + o_jac) : nullptr;
-    if (c->profiling) hipEventRecord(c->ev0, c->stream);
+    VILCHK(c->prof.mark(0, c->stream));
     hipLaunchKernelGGL(k_preint, dim3(n), dim3(PRE_THREADS), 0, c->stream, A);
-    if (c->profiling) hipEventRecord(c->ev1, c->stream);
-    VPCHK(hipMemcpyAsync(c->h + o_out, c->d_buf + o_out, (jacobian ? total : o_jac) - o_out, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(c->prof.mark(1, c->stream));
+    VILCHK(hipMemcpyAsync(c->h + o_out, c->d_buf + o_out, (jacobian ? total : o_jac) - o_out, hipMemcpyDeviceToHost, c->stream));
     const auto t3 = now();
-    VPCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
     const auto t4 = now();
-    VPCHK(hipGetLastError());
+    VILCHK(hipGetLastError());
     memcpy(imu_const, c->h + o_out, 8 * 287 * (size_t)n);
     if (jacobian) memcpy(jacobian, c->h + o_jac, 8 * 225 * (size_t)n);
     if (timing) fprintf(stderr, "vpre: stage %.1f h2d %.1f launch+d2h %.1f sync %.1f copy-out %.1f us\n", us(t0, t1), us(t1, t2), us(t2, t3), us(t3, t4), us(t4, now()));
-    if (c->profiling) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) { c->prof_ms += ms; c->prof_n++; } }
-    return VP_OK;
+    c->prof.span(0, 0, 1);
+    return VIL_OK;
 }
 
 int vpre_profile_enable(vpre_ctx* c, int32_t enable) {
-    if (!c) return VP_ERR_INVALID;
-    VPCHK(hipSetDevice(c->device));
-    if (enable && !c->ev0) { VPCHK(hipEventCreate(&c->ev0)); VPCHK(hipEventCreate(&c->ev1)); }
-    c->profiling = enable != 0;
-    return VP_OK;
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(c->prof.enable(c->device, enable != 0));
+    return VIL_OK;
 }
 int vpre_profile_read(vpre_ctx* c, int64_t* launches, double* total_ms) {
-    if (!c || !launches || !total_ms) return VP_ERR_INVALID;
-    *launches = c->prof_n; *total_ms = c->prof_ms; c->prof_n = 0; c->prof_ms = 0.0;
-    return VP_OK;
+    if (!c || !launches || !total_ms) return VIL_ERR_INVALID_ARGUMENT;
+    c->prof.read(launches, total_ms);
+    return VIL_OK;
 }
 
 }  // extern "C"

@@ -28,6 +28,8 @@
 #include <cstring>
 
 #include "../../include/vilsc.h"
+#include "vil_host.hpp"
+#include "vil_math.hpp"
 
 #define SC_R VSC_NUM_RING
 #define SC_S VSC_NUM_SECTOR
@@ -38,7 +40,6 @@
 #define SC_EMPTY (~0ull)
 #define SC_BIG 10000000.0
 #define SC_MAX_BIN_BLOCKS 512
-#define SCCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (getenv("VIL_DEBUG")) fprintf(stderr, "vilsc.hip:%d: %s\n", __LINE__, hipGetErrorString(e_)); return VIL_ERR_DEVICE; } } while (0)
 
 namespace {
 
@@ -108,14 +109,10 @@ __global__ __launch_bounds__(256) void k_sc_finish(const unsigned* __restrict__ 
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
-    for (int o = 32; o; o >>= 1) { const unsigned long long w = __shfl_xor(v, o); v = w < v ? w : v; }
-    return v;
-}
 // minimum over a 256-thread workgroup; `slot` (4 words) must not be one of the two slots used by the two previous calls' readers:
 // callers alternate between two slots, one barrier per call
 __device__ __forceinline__ unsigned long long block_min64(unsigned long long v, unsigned long long* slot) {
-    v = wave_min64(v);
+    v = vd::wave_min64(v);
     if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
     __syncthreads();
     unsigned long long m = slot[0];
@@ -272,8 +269,6 @@ __global__ __launch_bounds__(256) void k_sc_decide(int mode, int n_scored, int n
     }
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 bool config_ok(const vsc_config& c) {
     return std::isfinite(c.lidar_height) && std::isfinite(c.max_radius) && c.max_radius > 0.0 && !std::isnan(c.dist_thres) && c.search_ratio >= 0.0 && c.search_ratio <= 1.0 &&
            c.num_exclude_recent >= 0 && c.num_candidates >= 1 && c.num_candidates <= SC_K;
@@ -281,31 +276,26 @@ bool config_ok(const vsc_config& c) {
 
 }  // namespace
 
-struct vsc_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vsc_ctx : vilhost::Device {           // d_mem: descriptors | ring keys | sector keys | norms | points | staging | raw | partial lists | candidates | dist | shift | record
     vsc_config cfg;
     int max_entries = 0, max_points = 0, count = 0, radius = 0, n_parts = 0;
-    char* d_mem = nullptr;                                  // descriptors | ring keys | sector keys | norms | points | staging | raw | partial lists | candidates | dist | shift | record
     char* h_in = nullptr; vsc_result* h_res = nullptr;      // pinned: points or a descriptor up, the record down
     size_t o_desc = 0, o_ring = 0, o_sect = 0, o_norm = 0, o_pts = 0, o_stage = 0, o_raw = 0, o_part = 0, o_cand = 0, o_dist = 0, o_shift = 0, o_res = 0;
     int last_mode = 0, last_scored = 0;                     // what vsc_debug_read reads
-    bool profiling = false; hipEvent_t ev[5] = {}; long long prof_n[VSC_NUM_KERNELS] = {}; double prof_ms[VSC_NUM_KERNELS] = {};
+    vilhost::Profiler<VSC_NUM_KERNELS, 5> prof;
 };
 
 namespace {
-void prof_add(vsc_ctx* c, int first_event, const int* kernels, int n) {
-    for (int k = 0; k < n; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev[first_event + k], c->ev[first_event + k + 1]) == hipSuccess) { c->prof_ms[kernels[k]] += ms; c->prof_n[kernels[k]]++; } }
-}
 // the common tail of the two pushes: k_sc_finish appends entry `count`.  Events: [0] k_sc_bin [1] k_sc_finish [2]
 int finish_push(vsc_ctx* c, const float* d_raw, bool with_bin, int32_t* id_out) {
     char* d = c->d_mem;
     hipLaunchKernelGGL(k_sc_finish, dim3(1), dim3(256), 0, c->stream, (const unsigned*)(d + c->o_stage), d_raw, c->count, (float*)(d + c->o_desc), (float*)(d + c->o_ring),
                        (double*)(d + c->o_sect), (double*)(d + c->o_norm));
-    if (c->profiling) SCCHK(hipEventRecord(c->ev[2], c->stream));
-    SCCHK(hipStreamSynchronize(c->stream));                 // the pinned upload buffer is free again; nothing is read back
-    SCCHK(hipGetLastError());
-    if (c->profiling) { const int ks[2] = {K_BIN, K_FINISH}; if (with_bin) prof_add(c, 0, ks, 2); else prof_add(c, 1, ks + 1, 1); }
+    VILCHK(c->prof.mark(2, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));                 // the pinned upload buffer is free again; nothing is read back
+    VILCHK(hipGetLastError());
+    if (with_bin) c->prof.span(K_BIN, 0, 1);
+    c->prof.span(K_FINISH, 1, 2);
     if (id_out) *id_out = c->count;
     c->count++;
     return VIL_OK;
@@ -324,58 +314,47 @@ int vsc_create(int32_t device, int32_t max_entries, int32_t max_points, const vs
     vsc_config cf; vsc_default_config(&cf);
     if (cfg) cf = *cfg;
     if (!config_ok(cf)) return VIL_ERR_INVALID_ARGUMENT;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VIL_ERR_DEVICE;      // no CPU fallback
-    SCCHK(hipSetDevice(device));
     vsc_ctx* c = new vsc_ctx();
-    c->device = device; c->cfg = cf; c->max_entries = max_entries; c->max_points = max_points;
+    c->cfg = cf; c->max_entries = max_entries; c->max_points = max_points;
     c->radius = (int)std::round(0.5 * cf.search_ratio * (double)SC_S);
     c->n_parts = (max_entries + SC_CHUNK - 1) / SC_CHUNK;
     const size_t E = (size_t)max_entries, N = (size_t)max_points;
-    size_t o = 0;
-    c->o_desc = o; o += 4 * SC_BINS * E;
-    c->o_ring = o; o += 4 * SC_R * E;
-    c->o_sect = o; o += 8 * SC_S * E;
-    c->o_norm = o; o += 8 * SC_S * E;
-    c->o_pts = o; o += 16 * N;
-    c->o_stage = o; o += 4 * SC_BINS;
-    c->o_raw = o; o += 4 * SC_BINS;
-    c->o_part = o; o += 8 * SC_K * (size_t)c->n_parts;
-    c->o_cand = o; o += 4 * SC_K;
-    c->o_dist = o; o += up16(8 * E);
-    c->o_shift = o; o += up16(4 * E);
-    c->o_res = o; o += up16(sizeof(vsc_result));
+    vilhost::Arena a;
+    c->o_desc = a.take(4 * SC_BINS * E);
+    c->o_ring = a.take(4 * SC_R * E);
+    c->o_sect = a.take(8 * SC_S * E);
+    c->o_norm = a.take(8 * SC_S * E);
+    c->o_pts = a.take(16 * N);
+    c->o_stage = a.take(4 * SC_BINS);
+    c->o_raw = a.take(4 * SC_BINS);
+    c->o_part = a.take(8 * SC_K * (size_t)c->n_parts);
+    c->o_cand = a.take(4 * SC_K);
+    c->o_dist = a.take(8 * E);
+    c->o_shift = a.take(4 * E);
+    c->o_res = a.take(sizeof(vsc_result));
     const size_t h_in = 16 * N > 4 * (size_t)SC_BINS ? 16 * N : 4 * (size_t)SC_BINS;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_mem, o) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_in, h_in, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void**)&c->h_res, sizeof(vsc_result), hipHostMallocDefault) != hipSuccess) {
-        vsc_destroy(c);
-        return VIL_ERR_DEVICE;
-    }
+    hipError_t err = c->open(device, a.bytes);
+    if (err == hipSuccess) err = c->pin(&c->h_in, h_in);
+    if (err == hipSuccess) err = c->pin(&c->h_res, sizeof(vsc_result));
+    if (err != hipSuccess) { vsc_destroy(c); VILCHK(err); }
     *out = c;
     return VIL_OK;
 }
 
 void vsc_destroy(vsc_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipFree(c->d_mem);
-    if (c->h_in) hipHostFree(c->h_in);
-    if (c->h_res) hipHostFree(c->h_res);
-    for (hipEvent_t e : c->ev) if (e) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 
 int vsc_profile_enable(vsc_ctx* c, int32_t enable) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    SCCHK(hipSetDevice(c->device));
-    if (enable && !c->ev[0]) for (hipEvent_t& e : c->ev) SCCHK(hipEventCreate(&e));
-    c->profiling = enable != 0;
+    VILCHK(c->prof.enable(c->device, enable != 0));
     return VIL_OK;
 }
 int vsc_profile_read(vsc_ctx* c, int64_t* launches6, double* total_ms6) {
     if (!c || !launches6 || !total_ms6) return VIL_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < VSC_NUM_KERNELS; ++k) { launches6[k] = c->prof_n[k]; total_ms6[k] = c->prof_ms[k]; c->prof_n[k] = 0; c->prof_ms[k] = 0.0; }
+    c->prof.read(launches6, total_ms6);
     return VIL_OK;
 }
 
@@ -388,29 +367,29 @@ int vsc_reset(vsc_ctx* c) {
 
 int vsc_push_scan(vsc_ctx* c, int32_t n, const float* xyzi, int32_t* id_out) {
     if (!c || n < 0 || n > c->max_points || (n && !xyzi) || c->count >= c->max_entries) return VIL_ERR_INVALID_ARGUMENT;
-    SCCHK(hipSetDevice(c->device));
+    VILCHK(hipSetDevice(c->device));
     char* d = c->d_mem;
     unsigned* d_stage = (unsigned*)(d + c->o_stage);
     if (n) {
         memcpy(c->h_in, xyzi, 16 * (size_t)n);
-        SCCHK(hipMemcpyAsync(d + c->o_pts, c->h_in, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        VILCHK(hipMemcpyAsync(d + c->o_pts, c->h_in, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
-    SCCHK(hipMemsetAsync(d_stage, 0, 4 * SC_BINS, c->stream));
-    if (c->profiling) SCCHK(hipEventRecord(c->ev[0], c->stream));
+    VILCHK(hipMemsetAsync(d_stage, 0, 4 * SC_BINS, c->stream));
+    VILCHK(c->prof.mark(0, c->stream));
     if (n) {
         const int blocks = (n + 255) / 256 < SC_MAX_BIN_BLOCKS ? (n + 255) / 256 : SC_MAX_BIN_BLOCKS;
         hipLaunchKernelGGL(k_sc_bin, dim3(blocks), dim3(256), 0, c->stream, n, (const float4*)(d + c->o_pts), c->cfg.lidar_height, c->cfg.max_radius, d_stage);
     }
-    if (c->profiling) SCCHK(hipEventRecord(c->ev[1], c->stream));
+    VILCHK(c->prof.mark(1, c->stream));
     return finish_push(c, nullptr, n > 0, id_out);
 }
 
 int vsc_push_descriptor(vsc_ctx* c, const float* desc, int32_t* id_out) {
     if (!c || !desc || c->count >= c->max_entries) return VIL_ERR_INVALID_ARGUMENT;
-    SCCHK(hipSetDevice(c->device));
+    VILCHK(hipSetDevice(c->device));
     memcpy(c->h_in, desc, 4 * SC_BINS);
-    SCCHK(hipMemcpyAsync(c->d_mem + c->o_raw, c->h_in, 4 * SC_BINS, hipMemcpyHostToDevice, c->stream));
-    if (c->profiling) SCCHK(hipEventRecord(c->ev[1], c->stream));
+    VILCHK(hipMemcpyAsync(c->d_mem + c->o_raw, c->h_in, 4 * SC_BINS, hipMemcpyHostToDevice, c->stream));
+    VILCHK(c->prof.mark(1, c->stream));
     return finish_push(c, (const float*)(c->d_mem + c->o_raw), false, id_out);
 }
 
@@ -422,33 +401,31 @@ int vsc_detect(vsc_ctx* c, int32_t mode, int32_t n_search, vsc_result* out) {
         return VIL_OK;
     }
     if (n_search < 0) n_search = c->count - c->cfg.num_exclude_recent;                             // >= 1
-    SCCHK(hipSetDevice(c->device));
+    VILCHK(hipSetDevice(c->device));
     char* d = c->d_mem;
     const int q = c->count - 1;
-    const bool ref = mode == VSC_MODE_REFERENCE, prof = c->profiling;
+    const bool ref = mode == VSC_MODE_REFERENCE;
     const int kc = c->cfg.num_candidates < n_search ? c->cfg.num_candidates : n_search;
     const int n_scored = ref ? kc : n_search;
     int* d_cand = (int*)(d + c->o_cand); double* d_dist = (double*)(d + c->o_dist); int* d_shift = (int*)(d + c->o_shift);
-    if (prof) SCCHK(hipEventRecord(c->ev[0], c->stream));
+    VILCHK(c->prof.mark(0, c->stream));
     if (ref) {
         const int parts = (n_search + SC_CHUNK - 1) / SC_CHUNK;                                     // <= n_parts
         hipLaunchKernelGGL(k_sc_cand, dim3(parts), dim3(256), 0, c->stream, n_search, q, kc, (const float*)(d + c->o_ring), (unsigned long long*)(d + c->o_part));
-        if (prof) SCCHK(hipEventRecord(c->ev[1], c->stream));
+        VILCHK(c->prof.mark(1, c->stream));
         hipLaunchKernelGGL(k_sc_select, dim3(1), dim3(256), 0, c->stream, parts * SC_K, kc, (const unsigned long long*)(d + c->o_part), d_cand);
-    } else if (prof) SCCHK(hipEventRecord(c->ev[1], c->stream));
-    if (prof) SCCHK(hipEventRecord(c->ev[2], c->stream));
+    } else VILCHK(c->prof.mark(1, c->stream));
+    VILCHK(c->prof.mark(2, c->stream));
     hipLaunchKernelGGL(k_sc_score, dim3(n_scored), dim3(256), 0, c->stream, mode, q, c->radius, d_cand, (const float*)(d + c->o_desc), (const double*)(d + c->o_sect),
                        (const double*)(d + c->o_norm), d_dist, d_shift);
-    if (prof) SCCHK(hipEventRecord(c->ev[3], c->stream));
+    VILCHK(c->prof.mark(3, c->stream));
     hipLaunchKernelGGL(k_sc_decide, dim3(1), dim3(256), 0, c->stream, mode, n_scored, n_search, c->cfg.dist_thres, d_cand, d_dist, d_shift, (vsc_result*)(d + c->o_res));
-    if (prof) SCCHK(hipEventRecord(c->ev[4], c->stream));
-    SCCHK(hipMemcpyAsync(c->h_res, d + c->o_res, sizeof(vsc_result), hipMemcpyDeviceToHost, c->stream));
-    SCCHK(hipStreamSynchronize(c->stream));
-    SCCHK(hipGetLastError());
-    if (prof) {
-        const int all[4] = {K_CAND, K_SELECT, K_SCORE, K_DECIDE};
-        if (ref) prof_add(c, 0, all, 4); else prof_add(c, 2, all + 2, 2);
-    }
+    VILCHK(c->prof.mark(4, c->stream));
+    VILCHK(hipMemcpyAsync(c->h_res, d + c->o_res, sizeof(vsc_result), hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipGetLastError());
+    if (ref) { c->prof.span(K_CAND, 0, 1); c->prof.span(K_SELECT, 1, 2); }
+    c->prof.span(K_SCORE, 2, 3); c->prof.span(K_DECIDE, 3, 4);
     *out = *c->h_res;
     c->last_scored = n_scored;
     return VIL_OK;
@@ -456,11 +433,11 @@ int vsc_detect(vsc_ctx* c, int32_t mode, int32_t n_search, vsc_result* out) {
 
 int vsc_read_entry(vsc_ctx* c, int32_t id, float* desc, float* ringkey20, double* sectorkey60) {
     if (!c || id < 0 || id >= c->count) return VIL_ERR_INVALID_ARGUMENT;
-    SCCHK(hipSetDevice(c->device));
-    if (desc) SCCHK(hipMemcpyAsync(desc, c->d_mem + c->o_desc + 4 * SC_BINS * (size_t)id, 4 * SC_BINS, hipMemcpyDeviceToHost, c->stream));
-    if (ringkey20) SCCHK(hipMemcpyAsync(ringkey20, c->d_mem + c->o_ring + 4 * SC_R * (size_t)id, 4 * SC_R, hipMemcpyDeviceToHost, c->stream));
-    if (sectorkey60) SCCHK(hipMemcpyAsync(sectorkey60, c->d_mem + c->o_sect + 8 * SC_S * (size_t)id, 8 * SC_S, hipMemcpyDeviceToHost, c->stream));
-    SCCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipSetDevice(c->device));
+    if (desc) VILCHK(hipMemcpyAsync(desc, c->d_mem + c->o_desc + 4 * SC_BINS * (size_t)id, 4 * SC_BINS, hipMemcpyDeviceToHost, c->stream));
+    if (ringkey20) VILCHK(hipMemcpyAsync(ringkey20, c->d_mem + c->o_ring + 4 * SC_R * (size_t)id, 4 * SC_R, hipMemcpyDeviceToHost, c->stream));
+    if (sectorkey60) VILCHK(hipMemcpyAsync(sectorkey60, c->d_mem + c->o_sect + 8 * SC_S * (size_t)id, 8 * SC_S, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
     return VIL_OK;
 }
 
@@ -468,11 +445,11 @@ int vsc_debug_read(vsc_ctx* c, int32_t capacity, double* dist, int32_t* shift, i
     if (!c || capacity < c->last_scored) return VIL_ERR_INVALID_ARGUMENT;
     const int n = c->last_scored;
     if (n == 0) return VIL_OK;
-    SCCHK(hipSetDevice(c->device));
-    if (dist) SCCHK(hipMemcpyAsync(dist, c->d_mem + c->o_dist, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (shift) SCCHK(hipMemcpyAsync(shift, c->d_mem + c->o_shift, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (candidates && c->last_mode == VSC_MODE_REFERENCE) SCCHK(hipMemcpyAsync(candidates, c->d_mem + c->o_cand, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SCCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipSetDevice(c->device));
+    if (dist) VILCHK(hipMemcpyAsync(dist, c->d_mem + c->o_dist, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (shift) VILCHK(hipMemcpyAsync(shift, c->d_mem + c->o_shift, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (candidates && c->last_mode == VSC_MODE_REFERENCE) VILCHK(hipMemcpyAsync(candidates, c->d_mem + c->o_cand, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
     if (candidates && c->last_mode != VSC_MODE_REFERENCE) for (int i = 0; i < n; ++i) candidates[i] = i;
     return VIL_OK;
 }

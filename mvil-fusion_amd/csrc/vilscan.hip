@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "../../include/vilscan.h"
+#include "vil_host.hpp"
 
 #define VS_CAP VSCAN_MAX_RING_POINTS
 #define VS_THREADS 1024
@@ -32,9 +33,9 @@
 #define VS_EMPTY 0x7fffffff
 #define VS_OUTSIDE 3                 // label of a point that belongs to no processed subregion (reported as 0)
 #define VS_MAX_SUB 256
-#define VSCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (getenv("VIL_DEBUG")) fprintf(stderr, "vilscan.hip:%d: %s\n", __LINE__, hipGetErrorString(e_)); return VIL_ERR_DEVICE; } } while (0)
 
 namespace {
+using vilhost::up16;
 
 struct ScanP {
     int R, S, C, max_sharp, max_less, max_flat;
@@ -348,22 +349,17 @@ __global__ __launch_bounds__(256) void k_scan_gather(ScanP P, const int* __restr
     if (r + 1 == (int)gridDim.x && tid < 5) hdr[H_SHARP + tid] = s_pre[tid] + c[tid];
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
-struct vscan_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vscan_ctx : vilhost::Device {                        // d_mem: raw | ring bytes | staging | per-ring counts | result block
     vscan_config cfg;
     ScanP P;
     int max_points = 0;
     size_t cap_sharp = 0, cap_less = 0, cap_flat = 0;      // points: R x S x quota
     float* h_raw = nullptr;                                 // pinned upload image
-    char* d_mem = nullptr;                                  // raw | ring bytes | staging | per-ring counts | result block
     char* h_out = nullptr; size_t out_cap = 0;              // pinned mirror of the result block
     size_t o_raw = 0, o_id = 0, o_st_sharp = 0, o_st_less = 0, o_st_flat = 0, o_st_lf = 0, o_cnt = 0, o_out = 0;
-    bool profiling = false; hipEvent_t ev[VSCAN_NUM_KERNELS + 1] = {}; long long prof_n[VSCAN_NUM_KERNELS] = {}; double prof_ms[VSCAN_NUM_KERNELS] = {};
+    vilhost::Profiler<VSCAN_NUM_KERNELS, VSCAN_NUM_KERNELS + 1> prof;
 };
 
 namespace {
@@ -395,16 +391,14 @@ void vscan_default_config(vscan_config* cfg) {
 
 int vscan_create(int32_t device, const vscan_config* cfg, int32_t max_points, vscan_ctx** out) {
     if (!out || !cfg || max_points < 1) return VIL_ERR_INVALID_ARGUMENT;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VIL_ERR_DEVICE;      // no CPU fallback
+    if (!vilhost::has_device(device)) return VIL_ERR_DEVICE;
     if (cfg->uneven) return VIL_ERR_UNSUPPORTED;
     if (cfg->num_rings < 1 || cfg->num_rings > VSCAN_MAX_RINGS || !(cfg->upper_bound_deg > cfg->lower_bound_deg) || cfg->num_scan_subregions < 1 ||
         cfg->num_scan_subregions > VS_MAX_SUB || cfg->num_curvature_regions < 1 || cfg->num_curvature_regions > 32 || !std::isfinite(cfg->surf_curv_th) ||
         cfg->max_corner_sharp < 0 || cfg->max_corner_sharp > 4096 || cfg->max_corner_less_sharp < 0 || cfg->max_corner_less_sharp > 4096 || cfg->max_surf_flat < 0 ||
         cfg->max_surf_flat > 4096 || !(cfg->less_flat_filter_size > 0.0f) || !std::isfinite(cfg->less_flat_filter_size)) return VIL_ERR_INVALID_ARGUMENT;
-    VSCHK(hipSetDevice(device));
     vscan_ctx* c = new vscan_ctx();
-    c->device = device; c->cfg = *cfg; c->max_points = max_points;
+    c->cfg = *cfg; c->max_points = max_points;
     ScanP& P = c->P;
     P.R = cfg->num_rings; P.S = cfg->num_scan_subregions; P.C = cfg->num_curvature_regions;
     P.max_sharp = cfg->max_corner_sharp; P.max_less = cfg->max_corner_less_sharp; P.max_flat = cfg->max_surf_flat;
@@ -412,47 +406,38 @@ int vscan_create(int32_t device, const vscan_config* cfg, int32_t max_points, vs
     P.lower = (double)cfg->lower_bound_deg; P.factor = (double)(cfg->num_rings - 1) / ((double)cfg->upper_bound_deg - (double)cfg->lower_bound_deg);
     const size_t RS = (size_t)P.R * P.S, N = (size_t)max_points;
     c->cap_sharp = RS * P.max_sharp; c->cap_less = RS * P.max_less; c->cap_flat = RS * P.max_flat;
-    size_t o = 0;
-    c->o_raw = o; o += 16 * N;
-    c->o_id = o; o += up16(N + 4);
-    c->o_st_sharp = o; o += 16 * c->cap_sharp;
-    c->o_st_less = o; o += 16 * c->cap_less;
-    c->o_st_flat = o; o += 16 * c->cap_flat;
-    c->o_st_lf = o; o += 16 * N;
-    c->o_cnt = o; o += up16(4 * RC_INTS * (size_t)P.R);
-    c->o_out = o;
     c->out_cap = out_layout(c, max_points).bytes;
-    o += c->out_cap;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_mem, o) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_raw, 16 * N, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void**)&c->h_out, c->out_cap, hipHostMallocDefault) != hipSuccess) {
-        vscan_destroy(c);
-        return VIL_ERR_DEVICE;
-    }
+    vilhost::Arena a;
+    c->o_raw = a.take(16 * N);
+    c->o_id = a.take(N + 4);
+    c->o_st_sharp = a.take(16 * c->cap_sharp);
+    c->o_st_less = a.take(16 * c->cap_less);
+    c->o_st_flat = a.take(16 * c->cap_flat);
+    c->o_st_lf = a.take(16 * N);
+    c->o_cnt = a.take(4 * RC_INTS * (size_t)P.R);
+    c->o_out = a.take(c->out_cap);
+    hipError_t err = c->open(device, a.bytes);
+    if (err == hipSuccess) err = c->pin(&c->h_raw, 16 * N);
+    if (err == hipSuccess) err = c->pin(&c->h_out, c->out_cap);
+    if (err != hipSuccess) { vscan_destroy(c); VILCHK(err); }
     *out = c;
     return VIL_OK;
 }
 
 void vscan_destroy(vscan_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipFree(c->d_mem);
-    if (c->h_raw) hipHostFree(c->h_raw);
-    if (c->h_out) hipHostFree(c->h_out);
-    for (hipEvent_t e : c->ev) if (e) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 
 int vscan_profile_enable(vscan_ctx* c, int32_t enable) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    VSCHK(hipSetDevice(c->device));
-    if (enable && !c->ev[0]) for (hipEvent_t& e : c->ev) VSCHK(hipEventCreate(&e));
-    c->profiling = enable != 0;
+    VILCHK(c->prof.enable(c->device, enable != 0));
     return VIL_OK;
 }
 int vscan_profile_read(vscan_ctx* c, int64_t* launches4, double* total_ms4) {
     if (!c || !launches4 || !total_ms4) return VIL_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < VSCAN_NUM_KERNELS; ++k) { launches4[k] = c->prof_n[k]; total_ms4[k] = c->prof_ms[k]; c->prof_n[k] = 0; c->prof_ms[k] = 0.0; }
+    c->prof.read(launches4, total_ms4);
     return VIL_OK;
 }
 
@@ -463,29 +448,28 @@ int vscan_extract(vscan_ctx* c, int32_t n, const float* xyzi, vscan_result* out)
     int* hdr = (int*)c->h_out;
     if (n == 0) memset(c->h_out, 0, L.labels);             // nothing to submit: an empty table, no points
     else {
-        VSCHK(hipSetDevice(c->device));
+        VILCHK(hipSetDevice(c->device));
         memcpy(c->h_raw, xyzi, 16 * (size_t)n);
         char* d = c->d_mem; char* dout = d + c->o_out;
         const int npad = (n + 3) & ~3;
         float4* d_raw = (float4*)(d + c->o_raw); unsigned char* d_id = (unsigned char*)(d + c->o_id); int* d_cnt = (int*)(d + c->o_cnt);
         float4* st_sharp = (float4*)(d + c->o_st_sharp); float4* st_less = (float4*)(d + c->o_st_less); float4* st_flat = (float4*)(d + c->o_st_flat); float4* st_lf = (float4*)(d + c->o_st_lf);
         int* d_hdr = (int*)dout; int* d_table = (int*)(dout + L.table); signed char* d_labels = (signed char*)(dout + L.labels); float4* d_cloud = (float4*)(dout + L.cloud);
-        const bool prof = c->profiling;
-        VSCHK(hipMemcpyAsync(d_raw, c->h_raw, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        if (prof) VSCHK(hipEventRecord(c->ev[0], c->stream));
+        VILCHK(hipMemcpyAsync(d_raw, c->h_raw, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        VILCHK(c->prof.mark(0, c->stream));
         hipLaunchKernelGGL(k_scan_ring_id, dim3((npad + 255) / 256), dim3(256), 0, c->stream, n, npad, d_raw, d_id, P);
-        if (prof) VSCHK(hipEventRecord(c->ev[1], c->stream));
+        VILCHK(c->prof.mark(1, c->stream));
         hipLaunchKernelGGL(k_scan_ring_sort, dim3(P.R), dim3(VS_THREADS), 0, c->stream, npad, d_raw, d_id, d_table, d_cloud, d_hdr);
-        if (prof) VSCHK(hipEventRecord(c->ev[2], c->stream));
+        VILCHK(c->prof.mark(2, c->stream));
         hipLaunchKernelGGL(k_scan_features, dim3(P.R), dim3(VS_THREADS), 0, c->stream, P, d_table, d_cloud, d_labels, st_sharp, st_less, st_flat, st_lf, d_cnt, d_hdr);
-        if (prof) VSCHK(hipEventRecord(c->ev[3], c->stream));
+        VILCHK(c->prof.mark(3, c->stream));
         hipLaunchKernelGGL(k_scan_gather, dim3(P.R), dim3(256), 0, c->stream, P, d_table, d_cnt, st_sharp, st_less, st_flat, st_lf, (float4*)(dout + L.sharp), (float4*)(dout + L.less),
                            (float4*)(dout + L.flat), (float4*)(dout + L.lf), d_hdr);
-        if (prof) VSCHK(hipEventRecord(c->ev[4], c->stream));
-        VSCHK(hipMemcpyAsync(c->h_out, dout, L.bytes, hipMemcpyDeviceToHost, c->stream));
-        VSCHK(hipStreamSynchronize(c->stream));
-        VSCHK(hipGetLastError());
-        if (prof) for (int k = 0; k < VSCAN_NUM_KERNELS; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess) { c->prof_ms[k] += ms; c->prof_n[k]++; } }
+        VILCHK(c->prof.mark(4, c->stream));
+        VILCHK(hipMemcpyAsync(c->h_out, dout, L.bytes, hipMemcpyDeviceToHost, c->stream));
+        VILCHK(hipStreamSynchronize(c->stream));
+        VILCHK(hipGetLastError());
+        for (int k = 0; k < VSCAN_NUM_KERNELS; ++k) c->prof.span(k, k, k + 1);
     }
     const int nvalid = hdr[H_NVALID];
     out->num_rings = P.R; out->n_less_flat_raw = hdr[H_LFRAW];

@@ -25,17 +25,13 @@
 
 #include "../../include/vilvgicp.h"
 #include "vil_coop.hpp"
+#include "vil_host.hpp"
 #include "vil_knn.hpp"
 #include "vil_math.hpp"
 #include "vil_tuning.hpp"
 
-#define VG_OK 0
-#define VG_ERR_INVALID -1
-#define VG_ERR_DEVICE -2
-#define VG_ERR_NONFINITE -3
 #define VG_THREADS 256
 #define VGA_THREADS 512     // k_vgicp_align: one slot per thread on the usual scan (a pass is a chain of dependent gathers per slot; two waves per SIMD hide part of it)
-#define VGCHK(x) do { if ((x) != hipSuccess) return VG_ERR_DEVICE; } while (0)
 
 namespace {
 
@@ -289,9 +285,7 @@ struct HostKeyHash { size_t operator()(long long k) const { return (size_t)hash_
 
 }  // namespace
 
-struct vgicp_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vgicp_ctx : vilhost::Device {                 // d_mem is d_out; everything else grows on demand
     // target voxel map
     double res = 1.0; int nvox = 0, cap = 0;
     long long* d_keys = nullptr; int* d_slot = nullptr; int* d_num = nullptr; double* d_mean = nullptr; double* d_cov = nullptr; double* d_wsq = nullptr;
@@ -303,7 +297,7 @@ struct vgicp_ctx {
     int slots_cap2 = 0; int* d_cvox2 = nullptr; double* d_cM2 = nullptr;            // second correspondence cache of k_vgicp_align (speculative linearisation)
     double* d_part = nullptr; int part_cap = 0; double* d_out = nullptr; double* h_out = nullptr;
     bool linearized = false;
-    bool profiling = false; hipEvent_t ev0 = nullptr, ev1 = nullptr; long long prof_n = 0; double prof_ms = 0.0;
+    vilhost::Profiler<1, 2> prof;                      // k_vgicp_lin
     void* d_coop = nullptr; void* d_aout = nullptr; void* h_aout = nullptr; int coop_epoch = 0;       // one-launch alignment (k_vgicp_align)
     // neighbour search of the covariance estimation
     vknn::GridBuild gb; float grid_h = 1.0f; int grid_min = 4096; int coop_cap = -1; int* d_nn = nullptr; size_t nn_cap = 0;
@@ -317,20 +311,20 @@ static VoxTab tab(const vgicp_ctx* c) { return VoxTab{c->d_keys, c->d_slot, c->c
 
 // device covariances of a device-resident cloud (d_xyz) into d_cov (n x 9)
 static int covariances_dev(vgicp_ctx* c, int n, const float* d_xyz, int k, double* d_cov) {
-    if (k < 1 || k > KNN_MAX) return VG_ERR_INVALID;
+    if (k < 1 || k > KNN_MAX) return VIL_ERR_INVALID_ARGUMENT;
     const int nblk = (n + VG_THREADS - 1) / VG_THREADS;
     const int grid_min = c->grid_min;                            // below this the O(n^2) tiled search is faster than building the grid (vgicp_set_knn_grid)
     if (n < grid_min) {
         hipLaunchKernelGGL(k_knn_cov, dim3(nblk), dim3(VG_THREADS), 0, c->stream, n, d_xyz, k, d_cov);
     } else {
-        if ((size_t)n * KNN_MAX * 4 > c->nn_cap) { hipFree(c->d_nn); c->d_nn = nullptr; c->nn_cap = 0; VGCHK(hipMalloc(&c->d_nn, (size_t)n * KNN_MAX * 6)); c->nn_cap = (size_t)n * KNN_MAX * 6; }
-        VGCHK(vknn::grid_build_adaptive(c->gb, n, d_xyz, 3, c->grid_h, 8.0, c->stream));
+        if ((size_t)n * KNN_MAX * 4 > c->nn_cap) { hipFree(c->d_nn); c->d_nn = nullptr; c->nn_cap = 0; VILCHK(hipMalloc(&c->d_nn, (size_t)n * KNN_MAX * 6)); c->nn_cap = (size_t)n * KNN_MAX * 6; }
+        VILCHK(vknn::grid_build_adaptive(c->gb, n, d_xyz, 3, c->grid_h, 8.0, c->stream));
         hipLaunchKernelGGL(k_knn_wave, dim3((n + VG_QPB - 1) / VG_QPB), dim3(64 * VG_QPB), 0, c->stream, n, d_xyz, c->gb.G, c->gb.order, c->gb.cxyz, k, c->d_nn);
         hipLaunchKernelGGL(k_knn_fit, dim3(nblk), dim3(VG_THREADS), 0, c->stream, n, d_xyz, c->d_nn, k, d_cov);
     }
-    VGCHK(hipStreamSynchronize(c->stream));
-    VGCHK(hipGetLastError());
-    return VG_OK;
+    VILCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipGetLastError());
+    return VIL_OK;
 }
 
 // the fixed-order sum of the workgroup partials, result in c->h_out: polled from pinned memory (profiling / VIL_NO_POLL: copy + synchronise)
@@ -343,7 +337,7 @@ static hipError_t sum_and_fetch(vgicp_ctx* c, int nblk) {
         } else c->h_lin = nullptr;
         c->lin_tag = 1;
     }
-    if (c->h_lin && !c->profiling) {
+    if (c->h_lin && !c->prof.on) {
         const int tag = ++c->lin_tag;
         volatile int* seq = (volatile int*)(c->h_lin + 8 * 32);
         hipLaunchKernelGGL((k_vgicp_sum<NV>), dim3(1), dim3(VG_THREADS), 0, c->stream, nblk, c->d_part, c->d_out, (double*)c->d_lin, (int*)((char*)c->d_lin + 8 * 32), tag);
@@ -365,38 +359,35 @@ static hipError_t sum_and_fetch(vgicp_ctx* c, int nblk) {
 extern "C" {
 
 int vgicp_covariances(vgicp_ctx* c, int32_t n, const float* xyz, int32_t k, double* out) {
-    if (!c || n <= 0 || !xyz || !out) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
+    if (!c || n <= 0 || !xyz || !out) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     float* dx = nullptr; double* dc = nullptr;
-    VGCHK(hipMalloc(&dx, 12 * (size_t)n));
-    if (hipMalloc(&dc, 72 * (size_t)n) != hipSuccess) { hipFree(dx); return VG_ERR_DEVICE; }
-    int st = hipMemcpy(dx, xyz, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess ? covariances_dev(c, n, dx, k, dc) : VG_ERR_DEVICE;
-    if (st == VG_OK && hipMemcpy(out, dc, 72 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) st = VG_ERR_DEVICE;
+    VILCHK(hipMalloc(&dx, 12 * (size_t)n));
+    if (hipMalloc(&dc, 72 * (size_t)n) != hipSuccess) { hipFree(dx); return VIL_ERR_DEVICE; }
+    int st = hipMemcpy(dx, xyz, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess ? covariances_dev(c, n, dx, k, dc) : VIL_ERR_DEVICE;
+    if (st == VIL_OK && hipMemcpy(out, dc, 72 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) st = VIL_ERR_DEVICE;
     hipFree(dx); hipFree(dc);
     return st;
 }
 
 int vgicp_create(int32_t device, vgicp_ctx** out) {
-    if (!out) return VG_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VG_ERR_DEVICE;      // no CPU fallback
-    VGCHK(hipSetDevice(device));
+    if (!out) return VIL_ERR_INVALID_ARGUMENT;
     vgicp_ctx* c = new vgicp_ctx();
-    c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VG_ERR_DEVICE; }
-    if (hipMalloc(&c->d_out, 8 * 32) != hipSuccess || hipHostMalloc(&c->h_out, 8 * 32) != hipSuccess) { delete c; return VG_ERR_DEVICE; }
+    hipError_t err = c->open(device, 8 * 32);
+    if (err == hipSuccess) err = c->pin(&c->h_out, 8 * 32);
+    if (err != hipSuccess) { c->close(c->prof); delete c; VILCHK(err); }
+    c->d_out = (double*)c->d_mem;
     *out = c;
-    return VG_OK;
+    return VIL_OK;
 }
 void vgicp_destroy(vgicp_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     free_target(c); free_source(c);
-    hipFree(c->d_cvox); hipFree(c->d_cM); hipFree(c->d_cvox2); hipFree(c->d_cM2); hipFree(c->d_part); hipFree(c->d_out); if (c->h_out) hipHostFree(c->h_out);
+    hipFree(c->d_cvox); hipFree(c->d_cM); hipFree(c->d_cvox2); hipFree(c->d_cM2); hipFree(c->d_part);
     hipFree(c->gb.ws); hipFree(c->d_nn);
     if (c->d_coop) hipFree(c->d_coop); if (c->h_aout) hipHostFree(c->h_aout); if (c->h_lin) hipHostFree(c->h_lin);
-    if (c->ev0) { hipEventDestroy(c->ev0); hipEventDestroy(c->ev1); }
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->close(c->prof);
     delete c;
 }
 void vgicp_default_options(vgicp_options* o) {
@@ -406,18 +397,18 @@ void vgicp_default_options(vgicp_options* o) {
 }
 
 int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* cov9_in, double resolution) {
-    if (!c || n <= 0 || !xyz || !(resolution > 0.0)) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
+    if (!c || n <= 0 || !xyz || !(resolution > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     std::vector<double> own;
     const double* cov9 = cov9_in;
-    if (!cov9) { own.resize(9 * (size_t)n); const int st = vgicp_covariances(c, n, xyz, KNN_MAX, own.data()); if (st != VG_OK) return st; cov9 = own.data(); }
+    if (!cov9) { own.resize(9 * (size_t)n); const int st = vgicp_covariances(c, n, xyz, KNN_MAX, own.data()); if (st != VIL_OK) return st; cov9 = own.data(); }
     // GaussianVoxelMap::create_voxelmap (fast_vgicp_voxel.hpp:128-159), ADDITIVE voxels: sequential sums in point order
     std::unordered_map<long long, int, HostKeyHash> index;
     std::vector<long long> keys; std::vector<int> num; std::vector<double> mean, cov;
     index.reserve((size_t)n);
     for (int i = 0; i < n; ++i) {
         const double p[3] = {(double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2]};
-        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return VG_ERR_NONFINITE;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return VIL_ERR_NON_FINITE;
         const long long k = pack_key((int)std::floor(p[0] / resolution - 0.5), (int)std::floor(p[1] / resolution - 0.5), (int)std::floor(p[2] / resolution - 0.5));
         auto it = index.find(k);
         int v;
@@ -433,41 +424,41 @@ int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* co
     std::vector<long long> tkeys((size_t)cap, -1); std::vector<int> tslot((size_t)cap, -1);
     for (int v = 0; v < nv; ++v) { unsigned h = hash_key(keys[v]) & (cap - 1); while (tkeys[h] >= 0) h = (h + 1) & (cap - 1); tkeys[h] = keys[v]; tslot[h] = v; }
     free_target(c);
-    VGCHK(hipMalloc(&c->d_keys, 8 * (size_t)cap)); VGCHK(hipMalloc(&c->d_slot, 4 * (size_t)cap)); VGCHK(hipMalloc(&c->d_num, 4 * (size_t)nv));
-    VGCHK(hipMalloc(&c->d_mean, 8 * 3 * (size_t)nv)); VGCHK(hipMalloc(&c->d_cov, 8 * 9 * (size_t)nv));
-    VGCHK(hipMemcpy(c->d_keys, tkeys.data(), 8 * (size_t)cap, hipMemcpyHostToDevice)); VGCHK(hipMemcpy(c->d_slot, tslot.data(), 4 * (size_t)cap, hipMemcpyHostToDevice));
-    { std::vector<double> wsq((size_t)nv); for (int v = 0; v < nv; ++v) wsq[v] = std::sqrt((double)num[v]); VGCHK(hipMalloc(&c->d_wsq, 8 * (size_t)nv)); VGCHK(hipMemcpy(c->d_wsq, wsq.data(), 8 * (size_t)nv, hipMemcpyHostToDevice)); }
-    VGCHK(hipMemcpy(c->d_num, num.data(), 4 * (size_t)nv, hipMemcpyHostToDevice)); VGCHK(hipMemcpy(c->d_mean, mean.data(), 8 * 3 * (size_t)nv, hipMemcpyHostToDevice));
-    VGCHK(hipMemcpy(c->d_cov, cov.data(), 8 * 9 * (size_t)nv, hipMemcpyHostToDevice));
+    VILCHK(hipMalloc(&c->d_keys, 8 * (size_t)cap)); VILCHK(hipMalloc(&c->d_slot, 4 * (size_t)cap)); VILCHK(hipMalloc(&c->d_num, 4 * (size_t)nv));
+    VILCHK(hipMalloc(&c->d_mean, 8 * 3 * (size_t)nv)); VILCHK(hipMalloc(&c->d_cov, 8 * 9 * (size_t)nv));
+    VILCHK(hipMemcpy(c->d_keys, tkeys.data(), 8 * (size_t)cap, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(c->d_slot, tslot.data(), 4 * (size_t)cap, hipMemcpyHostToDevice));
+    { std::vector<double> wsq((size_t)nv); for (int v = 0; v < nv; ++v) wsq[v] = std::sqrt((double)num[v]); VILCHK(hipMalloc(&c->d_wsq, 8 * (size_t)nv)); VILCHK(hipMemcpy(c->d_wsq, wsq.data(), 8 * (size_t)nv, hipMemcpyHostToDevice)); }
+    VILCHK(hipMemcpy(c->d_num, num.data(), 4 * (size_t)nv, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(c->d_mean, mean.data(), 8 * 3 * (size_t)nv, hipMemcpyHostToDevice));
+    VILCHK(hipMemcpy(c->d_cov, cov.data(), 8 * 9 * (size_t)nv, hipMemcpyHostToDevice));
     c->res = resolution; c->nvox = nv; c->cap = cap; c->linearized = false;
-    return VG_OK;
+    return VIL_OK;
 }
 
 int vgicp_set_source(vgicp_ctx* c, int32_t n, const float* xyz, const double* cov9) {
-    if (!c || n <= 0 || !xyz) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
+    if (!c || n <= 0 || !xyz) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     free_source(c);
-    VGCHK(hipMalloc(&c->d_sxyz, 4 * 3 * (size_t)n)); VGCHK(hipMalloc(&c->d_scov, 8 * 9 * (size_t)n));
-    VGCHK(hipMemcpy(c->d_sxyz, xyz, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
-    if (cov9) VGCHK(hipMemcpy(c->d_scov, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
-    else { const int st = covariances_dev(c, n, c->d_sxyz, KNN_MAX, c->d_scov); if (st != VG_OK) return st; }      // source covariances never leave the device
+    VILCHK(hipMalloc(&c->d_sxyz, 4 * 3 * (size_t)n)); VILCHK(hipMalloc(&c->d_scov, 8 * 9 * (size_t)n));
+    VILCHK(hipMemcpy(c->d_sxyz, xyz, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
+    if (cov9) VILCHK(hipMemcpy(c->d_scov, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
+    else { const int st = covariances_dev(c, n, c->d_sxyz, KNN_MAX, c->d_scov); if (st != VIL_OK) return st; }      // source covariances never leave the device
     c->n = n; c->linearized = false;
-    return VG_OK;
+    return VIL_OK;
 }
 
 int vgicp_linearize(vgicp_ctx* c, const double* T, int32_t mode, double* err, double* H, double* b, int32_t* n_corr) {
-    if (!c || !T || !err || !c->nvox || !c->n || (mode != VGICP_DIRECT1 && mode != VGICP_DIRECT7 && mode != VGICP_DIRECT27)) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
+    if (!c || !T || !err || !c->nvox || !c->n || (mode != VGICP_DIRECT1 && mode != VGICP_DIRECT7 && mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     const int slots = c->n * mode, nblk = (slots + VG_THREADS - 1) / VG_THREADS;
-    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VGCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VGCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
-    if (nblk > c->part_cap) { hipFree(c->d_part); c->d_part = nullptr; c->part_cap = 0; VGCHK(hipMalloc(&c->d_part, 8 * 29 * (size_t)nblk)); c->part_cap = nblk; }
+    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VILCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VILCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
+    if (nblk > c->part_cap) { hipFree(c->d_part); c->d_part = nullptr; c->part_cap = 0; VILCHK(hipMalloc(&c->d_part, 8 * 29 * (size_t)nblk)); c->part_cap = nblk; }
     const int want = (H && b) ? 1 : 0;
-    if (c->profiling) hipEventRecord(c->ev0, c->stream);
+    VILCHK(c->prof.mark(0, c->stream));
     hipLaunchKernelGGL(k_vgicp_lin, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->n, (int)mode, c->d_sxyz, c->d_scov, to_iso(T), c->res, tab(c), c->d_cvox, c->d_cM, c->d_part, want);
-    if (c->profiling) hipEventRecord(c->ev1, c->stream);
-    VGCHK(sum_and_fetch<29>(c, nblk));
-    VGCHK(hipGetLastError());
-    if (c->profiling) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) { c->prof_ms += ms; c->prof_n++; } }
+    VILCHK(c->prof.mark(1, c->stream));
+    VILCHK(sum_and_fetch<29>(c, nblk));
+    VILCHK(hipGetLastError());
+    c->prof.span(0, 0, 1);
     c->noff = mode; c->slots = slots; c->linearized = true;
     *err = c->h_out[27];
     if (n_corr) *n_corr = (int32_t)c->h_out[28];
@@ -475,30 +466,28 @@ int vgicp_linearize(vgicp_ctx* c, const double* T, int32_t mode, double* err, do
         int idx = 0;
         for (int p = 0; p < 6; ++p) { for (int q = p; q < 6; ++q) { H[6 * p + q] = c->h_out[idx]; H[6 * q + p] = c->h_out[idx]; ++idx; } b[p] = c->h_out[21 + p]; }
     }
-    return std::isfinite(*err) ? VG_OK : VG_ERR_NONFINITE;
+    return std::isfinite(*err) ? VIL_OK : VIL_ERR_NON_FINITE;
 }
 
 int vgicp_profile_enable(vgicp_ctx* c, int32_t enable) {
-    if (!c) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
-    if (enable && !c->ev0) { VGCHK(hipEventCreate(&c->ev0)); VGCHK(hipEventCreate(&c->ev1)); }
-    c->profiling = enable != 0;
-    return VG_OK;
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(c->prof.enable(c->device, enable != 0));
+    return VIL_OK;
 }
 int vgicp_profile_read(vgicp_ctx* c, int64_t* launches, double* total_ms) {
-    if (!c || !launches || !total_ms) return VG_ERR_INVALID;
-    *launches = c->prof_n; *total_ms = c->prof_ms; c->prof_n = 0; c->prof_ms = 0.0;
-    return VG_OK;
+    if (!c || !launches || !total_ms) return VIL_ERR_INVALID_ARGUMENT;
+    c->prof.read(launches, total_ms);
+    return VIL_OK;
 }
 
 int vgicp_compute_error(vgicp_ctx* c, const double* T, double* err) {
-    if (!c || !T || !err || !c->linearized) return VG_ERR_INVALID;
-    VGCHK(hipSetDevice(c->device));
+    if (!c || !T || !err || !c->linearized) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
     const int nblk = (c->slots + VG_THREADS - 1) / VG_THREADS;
     hipLaunchKernelGGL(k_vgicp_err, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->slots, c->noff, c->d_sxyz, to_iso(T), tab(c), c->d_cvox, c->d_cM, c->d_part);
-    VGCHK(sum_and_fetch<1>(c, nblk));
+    VILCHK(sum_and_fetch<1>(c, nblk));
     *err = c->h_out[0];
-    return std::isfinite(*err) ? VG_OK : VG_ERR_NONFINITE;
+    return std::isfinite(*err) ? VIL_OK : VIL_ERR_NON_FINITE;
 }
 
 // ---- host side of LsqRegistration (lsq_registration_impl.hpp:48-165): 6 x 6 algebra between device reductions --------------
@@ -793,7 +782,7 @@ __global__ __launch_bounds__(VGA_THREADS) void k_vgicp_align(int n, int noff, co
         for (int k = 0; k < 16; ++k) out->T[k] = L.x0[k];
         for (int k = 0; k < 36; ++k) out->H[k] = L.Hout[k];
         out->err = L.y0; out->iterations = L.it; out->converged = L.converged; out->n_corr = L.n_corr;
-        out->lm_failed = L.lm_failed > 0 ? 1 : 0; out->status = L.lm_failed < 0 ? VG_ERR_NONFINITE : VG_OK;
+        out->lm_failed = L.lm_failed > 0 ? 1 : 0; out->status = L.lm_failed < 0 ? VIL_ERR_NON_FINITE : VIL_OK;
         out->pad = cbuf;                                    // which cache holds the correspondences of the last linearisation used
         __threadfence_system();                             // the record is in (pinned) host memory before its sequence number
         __hip_atomic_store(&out->seq, epoch0 + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -805,20 +794,20 @@ extern "C" {
 static int vgicp_align_host(vgicp_ctx* c, const double* guess, const vgicp_options* o, double* T_out, vgicp_summary* out);
 
 int vgicp_set_knn_grid(vgicp_ctx* c, int32_t min_points, double cell) {
-    if (!c || min_points < 0 || !(cell > 0.0)) return VG_ERR_INVALID;
+    if (!c || min_points < 0 || !(cell > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
     c->grid_min = min_points; c->grid_h = (float)cell;
-    return VG_OK;
+    return VIL_OK;
 }
 
 int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, double* T_out, vgicp_summary* out) {
-    if (!c || !guess || !o || !T_out || !out) return VG_ERR_INVALID;
-    if (!c->nvox || !c->n || (o->neighbor_mode != VGICP_DIRECT1 && o->neighbor_mode != VGICP_DIRECT7 && o->neighbor_mode != VGICP_DIRECT27)) return VG_ERR_INVALID;
+    if (!c || !guess || !o || !T_out || !out) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c->nvox || !c->n || (o->neighbor_mode != VGICP_DIRECT1 && o->neighbor_mode != VGICP_DIRECT7 && o->neighbor_mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
     if (VIL_TUNE_ENV("VGICP_HOST_LOOP")) return vgicp_align_host(c, guess, o, T_out, out);       // the step logic on the host between launches (cross-check)
-    VGCHK(hipSetDevice(c->device));
+    VILCHK(hipSetDevice(c->device));
     const int mode = o->neighbor_mode, slots = c->n * mode, nblk = (slots + VGA_THREADS - 1) / VGA_THREADS;
-    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VGCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VGCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
-    if (slots > c->slots_cap2) { hipFree(c->d_cvox2); hipFree(c->d_cM2); c->d_cvox2 = nullptr; c->d_cM2 = nullptr; c->slots_cap2 = 0; VGCHK(hipMalloc(&c->d_cvox2, 4 * (size_t)c->slots_cap)); VGCHK(hipMalloc(&c->d_cM2, 8 * 9 * (size_t)c->slots_cap)); c->slots_cap2 = c->slots_cap; }
-    if (!c->d_coop) { VGCHK(hipMalloc(&c->d_coop, sizeof(VgCoop))); VGCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); VGCHK(hipHostMalloc(&c->h_aout, sizeof(VgAlignOut), hipHostMallocMapped)); VGCHK(hipHostGetDevicePointer(&c->d_aout, c->h_aout, 0)); c->coop_epoch = 0; }
+    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VILCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VILCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
+    if (slots > c->slots_cap2) { hipFree(c->d_cvox2); hipFree(c->d_cM2); c->d_cvox2 = nullptr; c->d_cM2 = nullptr; c->slots_cap2 = 0; VILCHK(hipMalloc(&c->d_cvox2, 4 * (size_t)c->slots_cap)); VILCHK(hipMalloc(&c->d_cM2, 8 * 9 * (size_t)c->slots_cap)); c->slots_cap2 = c->slots_cap; }
+    if (!c->d_coop) { VILCHK(hipMalloc(&c->d_coop, sizeof(VgCoop))); VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); VILCHK(hipHostMalloc(&c->h_aout, sizeof(VgAlignOut), hipHostMallocMapped)); VILCHK(hipHostGetDevicePointer(&c->d_aout, c->h_aout, 0)); c->coop_epoch = 0; }
     VgAlignOut* ho = (VgAlignOut*)c->h_aout;
     VgGuess gs; std::memcpy(gs.m, guess, sizeof gs.m);
     if (c->coop_cap < 0) c->coop_cap = vilcoop::capacity((const void*)k_vgicp_align, VGA_THREADS, 0, c->device);
@@ -830,7 +819,7 @@ int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, doubl
     ho->seq = -1;
     hipLaunchKernelGGL(k_vgicp_align, dim3(G), dim3(VGA_THREADS), 0, c->stream, c->n, mode, c->d_sxyz, c->d_scov, c->res, tab(c), c->d_cvox, c->d_cM, c->d_cvox2, c->d_cM2, *o, (VgCoop*)c->d_coop, c->coop_epoch, gs, (VgAlignOut*)c->d_aout);
     c->coop_epoch += 4 * (o->max_iterations * (o->lm_max_iterations + 1) + 4);      // epochs only grow: nothing to reset between calls
-    if (c->coop_epoch > (1 << 30)) { VGCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); c->coop_epoch = 0; }
+    if (c->coop_epoch > (1 << 30)) { VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); c->coop_epoch = 0; }
     {   // the kernel's last act is the record's sequence number in pinned memory: polling it returns a few microseconds before the
         // stream's completion signal would (the launch queue stays in order either way); a kernel that never gets there is left to
         // hipStreamSynchronize, which reports the fault
@@ -841,10 +830,10 @@ int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, doubl
             if (*seq == epoch_of_call + 1) { seen = true; break; }
             if ((spin & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
         }
-        if (!seen) VGCHK(hipStreamSynchronize(c->stream));
+        if (!seen) VILCHK(hipStreamSynchronize(c->stream));
         std::atomic_thread_fence(std::memory_order_acquire);
     }
-    VGCHK(hipGetLastError());
+    VILCHK(hipGetLastError());
     if (ho->pad) { std::swap(c->d_cvox, c->d_cvox2); std::swap(c->d_cM, c->d_cM2); std::swap(c->slots_cap, c->slots_cap2); }      // vgicp_error() after an alignment sees its last linearisation
     c->noff = mode; c->slots = slots; c->linearized = true;
     std::memset(out, 0, sizeof *out);
@@ -865,7 +854,7 @@ static int vgicp_align_host(vgicp_ctx* c, const double* guess, const vgicp_optio
         double H[36], b[6], d[6] = {0, 0, 0, 0, 0, 0}, nb[6], y0;
         int32_t nc = 0;
         int st = vgicp_linearize(c, x0, o->neighbor_mode, &y0, H, b, &nc);
-        if (st != VG_OK) return st;
+        if (st != VIL_OK) return st;
         out->n_correspondences = nc; out->final_error = y0;
         for (int k = 0; k < 6; ++k) nb[k] = -b[k];
         bool stepped = false;
@@ -881,7 +870,7 @@ static int vgicp_align_host(vgicp_ctx* c, const double* guess, const vgicp_optio
                 if (!solve6(Hl, nb, d)) { lambda = nu * lambda; nu = 2 * nu; continue; }
                 double xi[16], yi; compose(d, x0, xi);
                 st = vgicp_compute_error(c, xi, &yi);
-                if (st != VG_OK) return st;
+                if (st != VIL_OK) return st;
                 double den = 0; for (int k = 0; k < 6; ++k) den += d[k] * (lambda * d[k] - b[k]);
                 const double rho = (y0 - yi) / den;
                 if (rho < 0) {
@@ -900,7 +889,7 @@ static int vgicp_align_host(vgicp_ctx* c, const double* guess, const vgicp_optio
     }
     out->iterations = it; out->converged = converged ? 1 : 0;
     std::memcpy(T_out, x0, sizeof x0);
-    return VG_OK;
+    return VIL_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import scanreg
+from ._row import RowError, RowHandle
 from .vgicp import _rot
 
 
@@ -21,49 +22,27 @@ MIN_SPHERE = 10
 _FP = C.POINTER(C.c_float)
 
 
-class DepthRegError(RuntimeError):
-    def __init__(self, what, status):
-        super().__init__("vdepth_%s failed: status %d" % (what, status))
-        self.status = status
+class DepthRegError(RowError):
+    pass
 
 
 class Depths:
     """What one vdepth_register call returns: depth (float32 n_feat, -1 = none), n_cloud, n_in_view, n_sphere, n_with_depth."""
 
 
-class DepthReg:
+class DepthReg(RowHandle):
+    ERROR, KERNELS = DepthRegError, KERNELS
+
     def __init__(self, cdll, max_cloud_points=1 << 17, max_features=1024, device=0):
-        self.lib = cdll
+        super().__init__(cdll, "vdepth_")
         self.max_cloud_points, self.max_features = max_cloud_points, max_features
-        self.ctx = C.c_void_p()
         self._last = (0, 0)
-        st = self._f("create")(C.c_int32(device), C.c_int32(max_cloud_points), C.c_int32(max_features), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise DepthRegError("create", st)
-
-    def _f(self, name):
-        f = getattr(self.lib, "vdepth_" + name)
-        f.restype = C.c_int
-        return f
-
-    def close(self):
-        if self.ctx is not None:
-            f = self.lib.vdepth_destroy; f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.c_int32(device), C.c_int32(max_cloud_points), C.c_int32(max_features))
 
     def set_cloud(self, xyzi):
         """xyzi: n x 4 float32, world frame; stays on the device until the next set_cloud."""
         xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
-        st = self._f("set_cloud")(self.ctx, C.c_int32(len(xyzi)), xyzi.ctypes.data_as(_FP))
-        if st != 0:
-            raise DepthRegError("set_cloud", st)
+        self._call("set_cloud", C.c_int32(len(xyzi)), xyzi.ctypes.data_as(_FP))
 
     def register(self, world_to_lidar, lidar_to_view, feat_xyz, depth_out=None):
         """The two float32 3 x 4 matrices of view_matrices and n_feat x 3 features.  depth_out: a float32 array to write into (tests of
@@ -73,9 +52,7 @@ class DepthReg:
         n = len(feat)
         depth = depth_out if depth_out is not None else np.zeros(max(1, n), np.float32)
         s = VdepthSummary()
-        st = self._f("register")(self.ctx, m1.ctypes.data_as(_FP), m2.ctypes.data_as(_FP), C.c_int32(n), feat.ctypes.data_as(_FP), depth.ctypes.data_as(_FP), C.byref(s))
-        if st != 0:
-            raise DepthRegError("register", st)
+        self._call("register", m1.ctypes.data_as(_FP), m2.ctypes.data_as(_FP), C.c_int32(n), feat.ctypes.data_as(_FP), depth.ctypes.data_as(_FP), C.byref(s))
         out = Depths()
         out.depth = depth[:n].copy()
         out.n_cloud, out.n_in_view, out.n_sphere, out.n_with_depth = s.n_cloud, s.n_in_view, s.n_sphere, s.n_with_depth
@@ -86,23 +63,8 @@ class DepthReg:
         """(sphere n_sphere x 4 [x y z range] in emission order, nn3 n_feat x 3) of the last register."""
         ns, nf = self._last
         sphere = np.zeros((max(1, ns), 4), np.float32); nn3 = np.zeros((max(1, nf), 3), np.int32)
-        st = self._f("debug_read")(self.ctx, sphere.ctypes.data_as(_FP), C.c_int32(ns), nn3.ctypes.data_as(C.POINTER(C.c_int32)))
-        if st != 0:
-            raise DepthRegError("debug_read", st)
+        self._call("debug_read", sphere.ctypes.data_as(_FP), C.c_int32(ns), nn3.ctypes.data_as(C.POINTER(C.c_int32)))
         return sphere[:ns], nn3[:nf]
-
-    def profile_enable(self, on=True):
-        st = self._f("profile_enable")(self.ctx, C.c_int32(1 if on else 0))
-        if st != 0:
-            raise DepthRegError("profile_enable", st)
-
-    def profile_read(self):
-        """{kernel: (launches, total ms)} since the last read."""
-        n = (C.c_int64 * len(KERNELS))(); ms = (C.c_double * len(KERNELS))()
-        st = self._f("profile_read")(self.ctx, n, ms)
-        if st != 0:
-            raise DepthRegError("profile_read", st)
-        return {k: (int(n[i]), float(ms[i])) for i, k in enumerate(KERNELS)}
 
 
 # ---- the host side of get_depth: the two matrices -----------------------------------------------------------------------------

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
+from ._row import RowError, RowHandle
 from .vgicp import _rot
 
 
@@ -17,41 +18,19 @@ class VmapSummary(C.Structure):
                 ("t_associate_ms", C.c_double), ("t_prepare_ms", C.c_double), ("t_solve_ms", C.c_double)]
 
 
-class MapRegError(RuntimeError):
+class MapRegError(RowError):
     pass
 
 
 _dp, _fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
 
 
-class MapReg:
+class MapReg(RowHandle):
+    ERROR, KERNELS = MapRegError, ("k_map_search", "k_map_fit")
+
     def __init__(self, cdll, prefix="vmap_", device=0):
-        self.lib, self.prefix = cdll, prefix
-        self.ctx = C.c_void_p()
-        st = self._f("create")(C.c_int32(device), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise MapRegError("%screate failed: status %d (no HIP device? there is no CPU fallback)" % (prefix, st))
-
-    def _f(self, name):
-        f = getattr(self.lib, self.prefix + name)
-        f.restype = C.c_int
-        return f
-
-    def close(self):
-        if self.ctx is not None:
-            f = getattr(self.lib, self.prefix + "destroy"); f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, name, st):
-        if st != 0:
-            raise MapRegError("%s%s failed: status %d" % (self.prefix, name, st))
+        super().__init__(cdll, prefix)
+        self._create(C.c_int32(device), hint=" (no HIP device? there is no CPU fallback)")
 
     def set_map(self, corner, surf):
         corner = np.ascontiguousarray(corner, np.float32).reshape(-1, 4); surf = np.ascontiguousarray(surf, np.float32).reshape(-1, 4)

@@ -8,35 +8,22 @@ import ctypes as C
 import numpy as np
 
 from . import synth
+from ._row import RowError, RowHandle
 
 _dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 NOISE = np.array([synth.ACC_N, synth.GYR_N, synth.ACC_W, synth.GYR_W])
 
 
-class PreintError(RuntimeError):
+class PreintError(RowError):
     pass
 
 
-class Preint:
+class Preint(RowHandle):
+    ERROR, KERNELS = PreintError, ("k_preint",)
+
     def __init__(self, cdll, prefix="vpre_", device=0):
-        self.lib, self.prefix = cdll, prefix
-        self.ctx = C.c_void_p()
-        f = getattr(cdll, prefix + "create"); f.restype = C.c_int
-        st = f(C.c_int32(device), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise PreintError("%screate failed: status %d (no HIP device? there is no CPU fallback)" % (prefix, st))
-
-    def close(self):
-        if self.ctx is not None:
-            f = getattr(self.lib, self.prefix + "destroy"); f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cdll, prefix)
+        self._create(C.c_int32(device), hint=" (no HIP device? there is no CPU fallback)")
 
     def bind(self, start, dt, acc, gyr, acc0, gyr0, ba, bg, noise=NOISE, want_jacobian=True):
         """Pre-builds the C arguments; returns (call, records, jacobians): call() runs the integration into the two arrays.
@@ -44,14 +31,14 @@ class Preint:
         start = np.ascontiguousarray(start, np.int32); n = len(start) - 1
         a = [np.ascontiguousarray(x, np.float64) for x in (dt, acc, gyr, acc0, gyr0, ba, bg, noise)]
         out = np.zeros((max(n, 1), 287)); jac = np.zeros((max(n, 1), 225)) if want_jacobian else None
-        f = getattr(self.lib, self.prefix + "integrate"); f.restype = C.c_int
+        f = self._f("integrate")
         args = [self.ctx, C.c_int32(n), start.ctypes.data_as(_ip)] + [x.ctypes.data_as(_dp) for x in a] + [out.ctypes.data_as(_dp), jac.ctypes.data_as(_dp) if want_jacobian else None]
         keep = (start, a)
 
         def call(_keep=keep):
             st = f(*args)
-            if st != 0:
-                raise PreintError("%sintegrate failed: status %d" % (self.prefix, st))
+            if st != 0:                      # tested here as well: bench.py times call(), the usual path makes no second call
+                self._chk("integrate", st)
         return call, out[:n], (jac[:n].reshape(n, 15, 15) if want_jacobian else None)
 
     def integrate(self, start, dt, acc, gyr, acc0, gyr0, ba, bg, noise=NOISE, want_jacobian=True):

@@ -6,6 +6,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._row import RowError, RowHandle
+
 NUM_RING, NUM_SECTOR = 20, 60
 MAX_CANDIDATES = 16
 MODE_REFERENCE, MODE_EXHAUSTIVE = 0, 1
@@ -23,10 +25,8 @@ class VscResult(C.Structure):
                 ("yaw_diff_rad", C.c_float), ("pad", C.c_int32)]
 
 
-class ScanContextError(RuntimeError):
-    def __init__(self, what, status):
-        super().__init__("vsc_%s failed: status %d" % (what, status))
-        self.status = status
+class ScanContextError(RowError):
+    pass
 
 
 def default_config(cdll, **kw):
@@ -40,43 +40,22 @@ def default_config(cdll, **kw):
     return cfg
 
 
-class ScanContext:
+class ScanContext(RowHandle):
     """The resident database.  Keyword arguments beyond the sizes are fields of vsc_config (lidar_height, max_radius, dist_thres,
     search_ratio, num_exclude_recent, num_candidates)."""
+    ERROR, KERNELS = ScanContextError, KERNELS
 
     def __init__(self, cdll, max_entries=4096, max_points=1 << 17, device=0, **config):
-        self.lib = cdll
+        super().__init__(cdll, "vsc_")
         self.cfg = default_config(cdll, **config)
-        self.ctx = C.c_void_p()
         self._scored = 0
-        st = self._f("create")(C.c_int32(device), C.c_int32(max_entries), C.c_int32(max_points), C.byref(self.cfg), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise ScanContextError("create", st)
-
-    def _f(self, name):
-        f = getattr(self.lib, "vsc_" + name)
-        f.restype = C.c_int
-        return f
-
-    def close(self):
-        if self.ctx is not None:
-            f = self.lib.vsc_destroy; f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.c_int32(device), C.c_int32(max_entries), C.c_int32(max_points), C.byref(self.cfg))
 
     def push_scan(self, xyzi):
         """xyzi: n x 4 float32, sensor frame.  Returns the new entry's id."""
         xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
         out = C.c_int32(-1)
-        st = self._f("push_scan")(self.ctx, C.c_int32(len(xyzi)), xyzi.ctypes.data_as(_FP), C.byref(out))
-        if st != 0:
-            raise ScanContextError("push_scan", st)
+        self._call("push_scan", C.c_int32(len(xyzi)), xyzi.ctypes.data_as(_FP), C.byref(out))
         return out.value
 
     def push_descriptor(self, desc):
@@ -84,17 +63,13 @@ class ScanContext:
         desc = np.ascontiguousarray(desc, np.float32)
         assert desc.shape == (NUM_RING, NUM_SECTOR)
         out = C.c_int32(-1)
-        st = self._f("push_descriptor")(self.ctx, desc.ctypes.data_as(_FP), C.byref(out))
-        if st != 0:
-            raise ScanContextError("push_descriptor", st)
+        self._call("push_descriptor", desc.ctypes.data_as(_FP), C.byref(out))
         return out.value
 
     def detect(self, mode=MODE_REFERENCE, n_search=-1):
         """The newest entry against entries [0, n_search); n_search < 0: count - num_exclude_recent.  Returns a VscResult."""
         r = VscResult()
-        st = self._f("detect")(self.ctx, C.c_int32(mode), C.c_int32(n_search), C.byref(r))
-        if st != 0:
-            raise ScanContextError("detect", st)
+        self._call("detect", C.c_int32(mode), C.c_int32(n_search), C.byref(r))
         self._scored = 0 if r.n_searched == 0 else (min(self.cfg.num_candidates, r.n_searched) if mode == MODE_REFERENCE else r.n_searched)
         return r
 
@@ -102,40 +77,21 @@ class ScanContext:
         return self._f("count")(self.ctx)
 
     def reset(self):
-        st = self._f("reset")(self.ctx)
-        if st != 0:
-            raise ScanContextError("reset", st)
+        self._call("reset")
         self._scored = 0
 
     def read_entry(self, i):
         """(descriptor 20 x 60 float32, ring key 20 float32, sector key 60 float64) of entry i."""
         desc = np.zeros((NUM_RING, NUM_SECTOR), np.float32); rk = np.zeros(NUM_RING, np.float32); sk = np.zeros(NUM_SECTOR, np.float64)
-        st = self._f("read_entry")(self.ctx, C.c_int32(i), desc.ctypes.data_as(_FP), rk.ctypes.data_as(_FP), sk.ctypes.data_as(_DP))
-        if st != 0:
-            raise ScanContextError("read_entry", st)
+        self._call("read_entry", C.c_int32(i), desc.ctypes.data_as(_FP), rk.ctypes.data_as(_FP), sk.ctypes.data_as(_DP))
         return desc, rk, sk
 
     def debug_read(self):
         """(dist float64, shift int32, candidates int32) per scored entry of the last detect, in the order the decision visited them."""
         n = self._scored
         dist = np.zeros(max(1, n)); shift = np.zeros(max(1, n), np.int32); cand = np.zeros(max(1, n), np.int32)
-        st = self._f("debug_read")(self.ctx, C.c_int32(n), dist.ctypes.data_as(_DP), shift.ctypes.data_as(_IP), cand.ctypes.data_as(_IP))
-        if st != 0:
-            raise ScanContextError("debug_read", st)
+        self._call("debug_read", C.c_int32(n), dist.ctypes.data_as(_DP), shift.ctypes.data_as(_IP), cand.ctypes.data_as(_IP))
         return dist[:n], shift[:n], cand[:n]
-
-    def profile_enable(self, on=True):
-        st = self._f("profile_enable")(self.ctx, C.c_int32(1 if on else 0))
-        if st != 0:
-            raise ScanContextError("profile_enable", st)
-
-    def profile_read(self):
-        """{kernel: (launches, total ms)} since the last read."""
-        n = (C.c_int64 * len(KERNELS))(); ms = (C.c_double * len(KERNELS))()
-        st = self._f("profile_read")(self.ctx, n, ms)
-        if st != 0:
-            raise ScanContextError("profile_read", st)
-        return {k: (int(n[i]), float(ms[i])) for i, k in enumerate(KERNELS)}
 
 
 def rot_z(yaw):

@@ -7,6 +7,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._row import RowError, RowHandle
+
 
 class VscanConfig(C.Structure):
     _fields_ = [("num_rings", C.c_int32), ("lower_bound_deg", C.c_float), ("upper_bound_deg", C.c_float), ("num_scan_subregions", C.c_int32),
@@ -29,10 +31,8 @@ MAX_RING_POINTS = 4096
 CLOUDS = ("cloud", "corner_sharp", "corner_less_sharp", "surf_flat", "surf_less_flat")
 
 
-class ScanRegError(RuntimeError):
-    def __init__(self, what, status):
-        super().__init__("vscan_%s failed: status %d" % (what, status))
-        self.status = status
+class ScanRegError(RowError):
+    pass
 
 
 class Features:
@@ -51,32 +51,14 @@ def default_config(cdll, **kw):
     return cfg
 
 
-class ScanReg:
+class ScanReg(RowHandle):
+    ERROR, KERNELS = ScanRegError, KERNELS
+
     def __init__(self, cdll, cfg=None, max_points=1 << 17, device=0):
-        self.lib = cdll
+        super().__init__(cdll, "vscan_")
         self.cfg = cfg or default_config(cdll)
         self.max_points = max_points
-        self.ctx = C.c_void_p()
-        st = self._f("create")(C.c_int32(device), C.byref(self.cfg), C.c_int32(max_points), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise ScanRegError("create", st)
-
-    def _f(self, name):
-        f = getattr(self.lib, "vscan_" + name)
-        f.restype = C.c_int
-        return f
-
-    def close(self):
-        if self.ctx is not None:
-            f = self.lib.vscan_destroy; f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.c_int32(device), C.byref(self.cfg), C.c_int32(max_points))
 
     def capacities(self, n):
         """The largest count each output of an n-point scan can have."""
@@ -99,27 +81,12 @@ class ScanReg:
         table = np.zeros((self.cfg.num_rings, 2), np.int32); labels = np.zeros(max(1, cap.get("labels", n)), np.int8)
         res.ring_table = table.ctypes.data_as(C.POINTER(C.c_int32)); res.ring_capacity = cap.get("rings", self.cfg.num_rings)
         res.labels = labels.ctypes.data_as(C.POINTER(C.c_int8)); res.label_capacity = cap.get("labels", n)
-        st = self._f("extract")(self.ctx, C.c_int32(n), xyzi.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res))
-        if st != 0:
-            raise ScanRegError("extract", st)
+        self._call("extract", C.c_int32(n), xyzi.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res))
         out = Features()
         for name in CLOUDS:
             setattr(out, name, buf[name][:getattr(res, name).count].copy())
         out.ring_table = table; out.labels = labels[:res.cloud.count].copy(); out.n_less_flat_raw = res.n_less_flat_raw
         return out
-
-    def profile_enable(self, on=True):
-        st = self._f("profile_enable")(self.ctx, C.c_int32(1 if on else 0))
-        if st != 0:
-            raise ScanRegError("profile_enable", st)
-
-    def profile_read(self):
-        """{kernel: (launches, total ms)} since the last read."""
-        n = (C.c_int64 * len(KERNELS))(); ms = (C.c_double * len(KERNELS))()
-        st = self._f("profile_read")(self.ctx, n, ms)
-        if st != 0:
-            raise ScanRegError("profile_read", st)
-        return {k: (int(n[i]), float(ms[i])) for i, k in enumerate(KERNELS)}
 
 
 # ---- raw scan of a spinning LiDAR in the 20 x 20 x 5 m room of mapreg.make_map / vgicp.scan ---------------------------------

@@ -7,6 +7,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._row import RowError, RowHandle
+
 DIRECT1, DIRECT7, DIRECT27 = 1, 7, 27
 LM, GN = 0, 1
 
@@ -21,41 +23,19 @@ class VgicpSummary(C.Structure):
                 ("final_error", C.c_double), ("final_hessian", C.c_double * 36)]
 
 
-class VgicpError(RuntimeError):
+class VgicpError(RowError):
     pass
 
 
 _dp, _fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
 
 
-class Vgicp:
+class Vgicp(RowHandle):
+    ERROR, KERNELS = VgicpError, ("k_vgicp_lin",)
+
     def __init__(self, cdll, prefix="vgicp_", device=0):
-        self.lib, self.prefix = cdll, prefix
-        self.ctx = C.c_void_p()
-        st = self._f("create")(C.c_int32(device), C.byref(self.ctx))
-        if st != 0:
-            self.ctx = None
-            raise VgicpError("%screate failed: status %d (no HIP device? there is no CPU fallback)" % (prefix, st))
-
-    def _f(self, name):
-        fc = self.__dict__.setdefault("_fcache", {})
-        f = fc.get(name)
-        if f is None:
-            f = getattr(self.lib, self.prefix + name)
-            f.restype = C.c_int
-            fc[name] = f
-        return f
-
-    def close(self):
-        if self.ctx is not None:
-            f = getattr(self.lib, self.prefix + "destroy"); f.restype = None
-            f(self.ctx); self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cdll, prefix)
+        self._create(C.c_int32(device), hint=" (no HIP device? there is no CPU fallback)")
 
     def default_options(self, **kw):
         o = VgicpOptions()
@@ -66,10 +46,6 @@ class Vgicp:
                 raise AttributeError("vgicp_options has no field %r" % k)
             setattr(o, k, v)
         return o
-
-    def _chk(self, name, st):
-        if st != 0:
-            raise VgicpError("%s%s failed: status %d" % (self.prefix, name, st))
 
     def set_target(self, xyz, cov=None, resolution=0.5):
         """cov None: the library estimates the covariances itself (k = 20 neighbours, PLANE regularisation)."""

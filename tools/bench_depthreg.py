@@ -9,7 +9,6 @@ timed calls, as the node does it (once per LiDAR scan, not per image); vdepth_se
 counterpart of this stage (PCL is absent): the only CPU restatement is the Python one of tests/depthreg_ref.py, which is test
 infrastructure and not a timing baseline, so no speed-up is claimed."""
 import os
-import subprocess
 import sys
 import time
 
@@ -19,22 +18,10 @@ import numpy as np
 import __graft_entry__ as g; g.load_package()
 from mvil_fusion_amd import depthreg, lib
 from mvil_fusion_amd.vgicp import _rot
+from _rowbench import WARM, commit, device_name, profiled, timed, write
 
 N = max(200, int(sys.argv[1])) if len(sys.argv) > 1 else 300
-WARM = 20
 OUT = os.environ.get("OUT") or os.path.join(ROOT, "profiles", "depthreg.txt")
-
-
-def commit():
-    try:
-        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
-    except Exception:
-        return os.environ.get("VIL_COMMIT", "unknown (not a git checkout)")
-
-
-def device_name():
-    import torch
-    return torch.cuda.get_device_name(0)
 
 
 so = lib.load_vilsolve()
@@ -49,24 +36,10 @@ for n_poses, az, n_feat in ((7, 900, 150), (14, 1800, 600)):
     up = []
     for _ in range(WARM):
         a = time.perf_counter(); reg.set_cloud(cloud); up.append(time.perf_counter() - a)
-    for _ in range(WARM):
-        d = reg.register(m1, m2, feat)
-    ts = []
-    for _ in range(N):
-        a = time.perf_counter(); reg.register(m1, m2, feat); ts.append(time.perf_counter() - a)
-    ts = 1e3 * np.array(ts)
-    reg.profile_enable(True); reg.profile_read()
-    for _ in range(N):
-        reg.register(m1, m2, feat)
-    prof = reg.profile_read()
+    d, wall = timed(lambda: reg.register(m1, m2, feat), N)
+    kernels = profiled(reg, lambda: reg.register(m1, m2, feat), N)
     reg.close()
-    lines.append("%d points, %d features (%d in view, %d sphere points, %d with depth): wall median %.3f ms, mean %.3f, p90 %.3f, min %.3f; vdepth_set_cloud median %.3f ms" %
-                 (len(cloud), n_feat, d.n_in_view, d.n_sphere, d.n_with_depth, np.median(ts), ts.mean(), np.percentile(ts, 90), ts.min(), 1e3 * np.median(up[5:])))
-    for k in depthreg.KERNELS:
-        n, ms = prof[k]
-        lines.append("    %-18s %4d launches, %8.2f us per launch" % (k, n, 1e3 * ms / max(n, 1)))
-    lines.append("    kernels together %8.2f us per call" % (1e3 * sum(ms for _, ms in prof.values()) / N))
-text = "\n".join(lines) + "\n"
-print(text, end="")
-os.makedirs(os.path.dirname(OUT), exist_ok=True)
-open(OUT, "w").write(text)
+    lines.append("%d points, %d features (%d in view, %d sphere points, %d with depth): %s; vdepth_set_cloud median %.3f ms" %
+                 (len(cloud), n_feat, d.n_in_view, d.n_sphere, d.n_with_depth, wall, 1e3 * np.median(up[5:])))
+    lines += kernels
+write(lines, OUT)

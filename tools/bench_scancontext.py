@@ -18,27 +18,13 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import __graft_entry__ as g; g.load_package()
 from mvil_fusion_amd import lib, scancontext as sc
+from _rowbench import WARM, commit, device_name, profiled, timed, write
 
-WARM = 20
 OUT = os.environ.get("OUT") or os.path.join(ROOT, "profiles", "scancontext.txt")
 STEPS = (("push", 20000, 120), ("push", 100000, 120), ("detect", 1000, 180), ("detect", 10000, 300))     # (what, size, time limit in s)
 
 
-def commit():
-    try:
-        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
-    except Exception:
-        return os.environ.get("VIL_COMMIT", "unknown (not a git checkout)")
-
-
-def stats(ts):
-    ts = 1e3 * np.array(ts)
-    return "wall median %.3f ms, mean %.3f, p90 %.3f, min %.3f" % (np.median(ts), ts.mean(), np.percentile(ts, 90), ts.min())
-
-
-def kernel_lines(prof, calls):
-    out = ["    %-12s %5d launches, %8.2f us per launch" % (k, n, 1e3 * ms / n) for k, (n, ms) in prof.items() if n]
-    return out + ["    kernels together %8.2f us per call" % (1e3 * sum(ms for _, ms in prof.values()) / calls)]
+KERNEL_FMT = "    %-12s %5d launches, %8.2f us per launch"          # a line per kernel that ran: a push runs two of the six, a detect two or four
 
 
 def step_push(n_points, calls):
@@ -46,18 +32,12 @@ def step_push(n_points, calls):
     rng = np.random.default_rng(1)
     scan = rng.uniform(-68.0, 68.0, (n_points, 4)).astype(np.float32); scan[:, 2] = rng.uniform(-2.0, 8.0, n_points)
     ctx = sc.ScanContext(lib.load_vilsolve(), max_entries=2 * (calls + WARM), max_points=n_points)
-    for _ in range(WARM):
-        ctx.push_scan(scan)
-    ts = []
-    for _ in range(calls):
-        a = time.perf_counter(); ctx.push_scan(scan); ts.append(time.perf_counter() - a)
-    ctx.reset(); ctx.profile_enable(True); ctx.profile_read()
-    for _ in range(calls):
-        ctx.push_scan(scan)
-    prof = ctx.profile_read()
+    _, wall = timed(lambda: ctx.push_scan(scan), calls)
+    ctx.reset()
+    kernels = profiled(ctx, lambda: ctx.push_scan(scan), calls, fmt=KERNEL_FMT, idle=False)
     occupied = int((ctx.read_entry(0)[0] != 0).sum())
     ctx.close()
-    return ["vsc_push_scan, %d points (%d of 1200 bins occupied): %s" % (n_points, occupied, stats(ts))] + kernel_lines(prof, calls)
+    return ["vsc_push_scan, %d points (%d of 1200 bins occupied): %s" % (n_points, occupied, wall)] + kernels
 
 
 def step_detect(n_entries, calls):
@@ -72,17 +52,11 @@ def step_detect(n_entries, calls):
     ctx.push_descriptor(np.roll(base[3], 17, axis=1))
     lines = ["database of %d entries (filled through vsc_push_descriptor in %.2f s)" % (n_entries, fill)]
     for mode, name in ((sc.MODE_REFERENCE, "REFERENCE"), (sc.MODE_EXHAUSTIVE, "EXHAUSTIVE")):
-        for _ in range(WARM):
-            r = ctx.detect(mode)
-        ts = []
-        for _ in range(calls):
-            a = time.perf_counter(); ctx.detect(mode); ts.append(time.perf_counter() - a)
-        ctx.profile_enable(True); ctx.profile_read()
-        for _ in range(calls):
-            ctx.detect(mode)
-        prof = ctx.profile_read(); ctx.profile_enable(False)
-        lines.append("vsc_detect %s, %d searched (loop_id %d, min_dist %.3g, nn_align %d): %s" % (name, r.n_searched, r.loop_id, r.min_dist, r.nn_align, stats(ts)))
-        lines += kernel_lines(prof, calls)
+        r, wall = timed(lambda: ctx.detect(mode), calls)
+        kernels = profiled(ctx, lambda: ctx.detect(mode), calls, fmt=KERNEL_FMT, idle=False)
+        ctx.profile_enable(False)
+        lines.append("vsc_detect %s, %d searched (loop_id %d, min_dist %.3g, nn_align %d): %s" % (name, r.n_searched, r.loop_id, r.min_dist, r.nn_align, wall))
+        lines += kernels
     ctx.close()
     return lines
 
@@ -93,8 +67,7 @@ if __name__ == "__main__":
         print("\n".join(fn(int(sys.argv[3]), int(sys.argv[4]))))
         sys.exit(0)
     calls = max(50, int(sys.argv[1])) if len(sys.argv) > 1 else 200
-    import torch
-    lines = ["Scan Context row (include/vilsc.h), %d warm calls per figure after %d warm-up calls; %s; commit %s" % (calls, WARM, torch.cuda.get_device_name(0), commit()),
+    lines = ["Scan Context row (include/vilsc.h), %d warm calls per figure after %d warm-up calls; %s; commit %s" % (calls, WARM, device_name(), commit()),
              "wall = host clock around the call, events off; kernel = HIP events, second pass",
              "no CPU timing baseline exists for this stage: the only CPU restatement is tests/scancontext_ref.py (Python, test infrastructure)"]
     for what, size, limit in STEPS:
@@ -107,7 +80,4 @@ if __name__ == "__main__":
             lines.append("%s %d: exit status %d; the run ends here\n%s" % (what, size, p.returncode, p.stderr[-1000:]))
             break
         lines.append(p.stdout.rstrip("\n"))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    open(OUT, "w").write(text)
+    write(lines, OUT)
