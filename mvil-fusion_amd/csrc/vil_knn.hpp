@@ -1,4 +1,4 @@
-// vil_knn.hpp -- exact k-nearest-neighbour building blocks shared by the point-cloud rows (vilvgicp.hip, vilmap.hip):
+// vil_knn.hpp -- exact k-nearest-neighbour building blocks shared by the point-cloud rows (vilvgicp.hip, vilmap.hip, villoop.hip):
 // a register-resident sorted candidate list and a uniform grid built with atomics only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,14 @@ __device__ __forceinline__ void knn_insert(KnnList& L, float d, int j) {
 __device__ __forceinline__ float sqdist_nofma(float qx, float qy, float qz, float x, float y, float z) {
     const float dx = __fsub_rn(qx, x), dy = __fsub_rn(qy, y), dz = __fsub_rn(qz, z);
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));        // no fma: bit-equal to the CPU sum
+}
+// The intrinsics above are plain operators in the compiler's HIP headers, defined with contraction allowed, so the back end may still fuse
+// them (it does in places).  The same sum with contraction switched off where the operations are written: never an fma.  Rows that
+// promise the CPU's bits (villoop.hip) search with STRICT = true below; the others keep the code they were measured and pinned with.
+__device__ __forceinline__ float sqdist_strict(float qx, float qy, float qz, float x, float y, float z) {
+#pragma clang fp contract(off)
+    const float dx = qx - x, dy = qy - y, dz = qz - z;
+    return (dx * dx + dy * dy) + dz * dz;
 }
 // ---- uniform grid for larger clouds: count points per cell (hash table of packed cell keys), one atomic range claim per
 //      occupied cell, scatter into cell order; a query (knn_wave_query below) then walks Chebyshev rings of cells around its
@@ -119,14 +127,18 @@ __device__ __forceinline__ void knn_wave_offer(unsigned long long& best, unsigne
         m &= __ballot(key < thr);
     }
 }
+template <bool STRICT = false>
 __device__ __forceinline__ unsigned long long knn_wave_cand(int t, int total, float qx, float qy, float qz, const int* pos, const int* __restrict__ order, const float* __restrict__ cxyz) {
     if (t >= total) return ~0ull;
     const int j = pos ? pos[t] : t;
-    return knn_key(sqdist_nofma(qx, qy, qz, cxyz[3 * j], cxyz[3 * j + 1], cxyz[3 * j + 2]), order[j]);
+    const float x = cxyz[3 * j], y = cxyz[3 * j + 1], z = cxyz[3 * j + 2];
+    return knn_key(STRICT ? sqdist_strict(qx, qy, qz, x, y, z) : sqdist_nofma(qx, qy, qz, x, y, z), order[j]);
 }
 // Exact kk nearest neighbours (kk <= 64) of a WAVE-UNIFORM query; result: lane i < kk holds the i-th best key in `best`.
 // Returns false when the query is rejected early: everything unvisited is at least sqrt(reject_d2) away and the reject_k-th
 // best is not below reject_d2 (the callers discard such queries anyway).  wl: KNN_WL_CAP ints of LDS owned by this wave.
+// STRICT: distances by sqdist_strict.
+template <bool STRICT = false>
 __device__ __forceinline__ bool knn_wave_query(unsigned long long& best, float qx, float qy, float qz, int kk, int n, const GridTab& G, const int* __restrict__ order,
                                                const float* __restrict__ cxyz, int* wl, float reject_d2, int reject_k) {
     const int lane = threadIdx.x & 63;
@@ -160,13 +172,13 @@ __device__ __forceinline__ bool knn_wave_query(unsigned long long& best, float q
                 for (int u = 0; u < cnt; ++u) wl[excl + u] = b + u;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                for (int t0 = 0; t0 < total; t0 += 64) knn_wave_offer(best, knn_wave_cand(t0 + lane, total, qx, qy, qz, wl, order, cxyz), kk);
+                for (int t0 = 0; t0 < total; t0 += 64) knn_wave_offer(best, knn_wave_cand<STRICT>(t0 + lane, total, qx, qy, qz, wl, order, cxyz), kk);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             } else {
                 for (int c = 0; c < 64; ++c) {
                     const int cb = __builtin_amdgcn_readlane(b, c), cc = __builtin_amdgcn_readlane(cnt, c);
-                    for (int t0 = 0; t0 < cc; t0 += 64) knn_wave_offer(best, knn_wave_cand(cb + t0 + lane, cb + cc, qx, qy, qz, nullptr, order, cxyz), kk);
+                    for (int t0 = 0; t0 < cc; t0 += 64) knn_wave_offer(best, knn_wave_cand<STRICT>(cb + t0 + lane, cb + cc, qx, qy, qz, nullptr, order, cxyz), kk);
                 }
             }
         }
@@ -175,7 +187,7 @@ __device__ __forceinline__ bool knn_wave_query(unsigned long long& best, float q
         if (b2 >= reject_d2 && !(knn_key_d(readlane_u64(best, reject_k - 1)) < reject_d2)) return false;
     }
     best = ~0ull;
-    for (int t0 = 0; t0 < n; t0 += 64) knn_wave_offer(best, knn_wave_cand(t0 + lane, n, qx, qy, qz, nullptr, order, cxyz), kk);
+    for (int t0 = 0; t0 < n; t0 += 64) knn_wave_offer(best, knn_wave_cand<STRICT>(t0 + lane, n, qx, qy, qz, nullptr, order, cxyz), kk);
     return true;
 }
 
