@@ -269,66 +269,18 @@ int vil_comm_init_local(vil_ctx** ctxs, int n);
  * largest window, vil_reduced_dim(K)^2 + 3 D + 4 + 17 L + 6 F doubles) and returns its 64-byte IPC handle; the launcher gathers the
  * `world` handles in rank order (any transport) and every rank calls vil_comm_ipc_init.  Same sharding, same call sequence and the same
  * bit-identical results on every rank as with vil_comm_init; the collective is three small launches in stream order. */
+int vil_comm_ipc_export(vil_ctx* ctx, int rank, int world, size_t max_doubles, void* handle64);
+int vil_comm_ipc_init(vil_ctx* ctx, const void* handles /* world x 64 bytes */);
 /* What travels per trust-region iteration through these exchanges (and vil_comm_init_local): of the set [S' | g | cost | landmark arrays] the lower
  * triangle of S', the vectors and THIS RANK's slice of the landmark arrays (a landmark's entries are non-zero on its owner only: the sum over ranks is
  * the owner's value) -- 103 + 380 / world kB per peer at K = 10 / 1000 landmarks instead of 484 kB.  vil_comm_message_bytes reports it for the
  * uploaded (sharded) window. */
+/* RCCL (vil_comm_init, world <= 8) moves the same content as ONE ncclAllReduce of the packed camera part [lower(S') | g | b_c | diag | cost] plus ONE ncclAllGather
+ * of the owners' landmark slices (padded to the largest): 103 + 48 kB per rank at K = 10 / 1000 landmarks / world 8; vil_comm_message_bytes reports that sum. */
 int vil_comm_message_bytes(vil_ctx* ctx, int64_t* bytes_per_peer, int64_t* bytes_full_set);
 /* What the context's communicator is: its rank, the number of ranks it spans and the transport of the per-iteration collective (0: none, 1: RCCL,
  * 2: in-process, 3: peer buffers; -3: peer buffers exported but not yet initialised).  A launcher asserts world == the ranks it started. */
 int vil_comm_info(vil_ctx* ctx, int32_t* rank, int32_t* world, int32_t* transport);
-/* RCCL (vil_comm_init, world <= 8) moves the same content as ONE ncclAllReduce of the packed camera part [lower(S') | g | b_c | diag | cost] plus ONE ncclAllGather
- * of the owners' landmark slices (padded to the largest): 103 + 48 kB per rank at K = 10 / 1000 landmarks / world 8; vil_comm_message_bytes reports that sum.
- * test hook: the pack / unpack kernels of that path over the in-process communicator (two small kernels stand in for the RCCL calls), so that they run on
- * 2 / 3 / 8 ranks of one device. */
-int vil_debug_set_slim_emul(vil_ctx* ctx, int32_t on);
-int vil_comm_ipc_export(vil_ctx* ctx, int rank, int world, size_t max_doubles, void* handle64);
-int vil_comm_ipc_init(vil_ctx* ctx, const void* handles /* world x 64 bytes */);
-/* test hook: run the multi-GPU plumbing (partial system in set 0, the collective sums it into set 1, step kernel on set 1) on a
- * single rank, with or without a 1-rank communicator.  Invalidates the resident window. */
-int vil_debug_set_split(vil_ctx* ctx, int32_t on);
-/* test hook: which launch structure a single-GPU solve takes.  0 (default): the library's choice -- the whole iteration (sweep, gather, chain elimination, step)
- * in ONE launch whenever the device holds its waiting workgroups and the roles share one dynamic-LDS size (every BASELINE size on an MI355X), else the next one
- * down this list; 3: sweep launch + gather / step launch (round 4's structure); 1: the fallback for devices / windows where it does not: separate gather launch, the speed-bias chain
- * eliminated by a workgroup of the SWEEP launch; 2: no chain workgroup at all (the step kernel eliminates the chain itself, the round-2 structure).
- * 4: one launch per ITERATION (k_iter) also where the whole solve could run as one resident launch (k_solve: the default for windows whose every role fits the
- * device at once -- configs[1]; same bits as mode 4).
- * Same results to rounding in every mode.  Invalidates the resident window. */
-int vil_debug_set_launch_mode(vil_ctx* ctx, int32_t mode);
-/* test hook: the next n hipGraph captures of this context's solves are treated as failed (as a driver that cannot capture or instantiate the chunk would make them).
- * A failed capture is not an error: nothing has run yet, the solve at hand and every later solve of the context launch directly.  n = 0 re-arms graph replay. */
-int vil_debug_fail_graph_capture(vil_ctx* ctx, int32_t n);
-/* n resident windows (one context each, all on one device, each uploaded by vil_upload / vil_solve) solved CONCURRENTLY: a stream and a host thread per context, one
- * launch per trust-region iteration each.  One window keeps a single master workgroup busy for two thirds of an iteration; n of them interleave on the device -- what a
- * server that tracks several sessions on one GPU runs, and the single-GPU form of the `replicas` leg of bench.py --gpus N.  statuses[i] / summaries[i]: as
- * vil_solve_resident of context i; every window's result is bit-equal to its solo solve under vil_debug_set_launch_mode(4).  More windows than the device holds
- * waiting workgroups for are solved in groups: the waiting workgroups of a group fit the device per XCD and take at most half of it, counting the launches the runtime
- * runs together (its hardware queues: four, or GPU_MAX_HW_QUEUES).  Returns the first non-zero status. */
-int vil_solve_batch(vil_ctx** ctxs, int32_t n, const vil_options* options, vil_summary* summaries, int32_t* statuses);
-/* Recovery of a one-launch solve whose workgroups could not all run together.  The one-launch iteration's roles wait for one another inside the launch; every such
- * wait is bounded by TIME (50 ms of the device's 100 MHz wall clock).  A wait that gives up ends the launches at once; vil_solve_resident / vil_solve / vil_win_solve
- * then put the resident state back to what the solve started from and run the SAME solve again with two launches per iteration (sweep, then gather + step: mode 3 of
- * vil_debug_set_launch_mode -- same results to rounding), and return its result.  Only if that attempt gives up too is VIL_ERR_DEVICE returned -- with the resident
- * state (and the caller's vil_state) as the solve found them.  The next solve takes the one-launch structure again.
- * vil_recovery_counts: solves of this context that were re-run that way / that failed on both structures.
- * test hook vil_debug_drop_flag: in launch `launch` (0-based) of the NEXT solve, sweep role `role` (workgroup index in the sweep's order [imu | prior | rel | visual |
- * plane | edge]; -2 - g: gather workgroup g) does not post its completion flag -- what a workgroup that never became resident looks like to the ones waiting for it.
- * launch | 0x10000: a gather workgroup's flag is lost in the retry as well (a solve that fails on both structures). */
-int vil_debug_drop_flag(vil_ctx* ctx, int32_t role, int32_t launch);
-int vil_recovery_counts(vil_ctx* ctx, int64_t* recovered, int64_t* failed);
-/* profiling (with vil_profile_enable(ctx, 1), one-launch iterations): times == NULL arms it -- from now on every workgroup of launch `launch` (0-based) of a solve
- * leaves its entry and exit time (100 MHz device clock) --; with times != NULL the pairs {entry, exit} of the first max_workgroups (<= 4096) workgroups of the last
- * recorded launch are copied out, in block-index order = the launch's grid order [imu | prior | rel][chain][visual | plane | edge][master | helpers | tiles][gather]
- * (zeros: a workgroup that did not run).  tools/probe_workgroups.py prints them by role. */
-int vil_profile_workgroups(vil_ctx* ctx, int32_t launch, uint64_t* times, int32_t max_workgroups);
-/* test hook: the step's dense solve on a matrix of the caller's -- A is (D + 1) x (D + 1) row major, its lower triangle the SPD matrix, its last row the right-hand
- * side (D <= 159).  L receives the Cholesky factor (lower, row major, last row = L^-1 rhs), x the solution, *ok 0 when a pivot was not positive.  variant 1: what the
- * one-launch iteration runs (16-wide panels factored a matrix row per lane, back substitution a column per lane: vil_step.hpp chol_rowwave / back_subst_cols);
- * variant 0: the look-ahead factorisation (4-wide panels) and the back substitution through inverted diagonal tiles that the other launch structures run. */
-int vil_debug_dense_solve(vil_ctx* ctx, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant);
-/* what the uploaded window's solves launch per trust-region iteration: 0 (nothing: the whole solve is ONE resident launch, k_solve -- windows whose roles all fit the
- * device at once; *one_launch = 1 as well), 1 (the one-launch iteration), 2 (sweep + gather / step) or 3 (sweep, gather, step) */
-int vil_debug_get_launch_structure(vil_ctx* ctx, int32_t* launches_per_iteration, int32_t* one_launch);
 
 /* replaces estimator.cpp:1126-1419 (build ceres::Problem ... ceres::Solve): state is updated in
  * place on success and left UNCHANGED on any error. */
@@ -345,6 +297,21 @@ int vil_solve_resident(vil_ctx* ctx, const vil_options* options, vil_summary* su
 int vil_reset_state(vil_ctx* ctx);                       /* restore the uploaded state on device */
 int vil_download_state(vil_ctx* ctx, vil_state* state_out);
 
+/* n resident windows (one context each, all on one device, each uploaded by vil_upload / vil_solve) solved CONCURRENTLY: a stream and a host thread per context, one
+ * launch per trust-region iteration each.  One window keeps a single master workgroup busy for two thirds of an iteration; n of them interleave on the device -- what a
+ * server that tracks several sessions on one GPU runs, and the single-GPU form of the `replicas` leg of bench.py --gpus N.  statuses[i] / summaries[i]: as
+ * vil_solve_resident of context i; every window's result is bit-equal to its solo solve with one launch per iteration (launch mode 4 of vilsolve_debug.h).
+ * More windows than the device holds waiting workgroups for are solved in groups: the waiting workgroups of a group fit the device per XCD and take at most half of
+ * it, counting the launches the runtime runs together (its hardware queues: four, or GPU_MAX_HW_QUEUES).  Returns the first non-zero status. */
+int vil_solve_batch(vil_ctx** ctxs, int32_t n, const vil_options* options, vil_summary* summaries, int32_t* statuses);
+/* Recovery of a one-launch solve whose workgroups could not all run together.  The one-launch iteration's roles wait for one another inside the launch; every such
+ * wait is bounded by TIME (50 ms of the device's 100 MHz wall clock).  A wait that gives up ends the launches at once; vil_solve_resident / vil_solve / vil_win_solve
+ * then put the resident state back to what the solve started from and run the SAME solve again with two launches per iteration (sweep, then gather + step: launch
+ * mode 3 of vilsolve_debug.h -- same results to rounding), and return its result.  Only if that attempt gives up too is VIL_ERR_DEVICE returned -- with the resident
+ * state (and the caller's vil_state) as the solve found them.  The next solve takes the one-launch structure again.
+ * vil_recovery_counts: solves of this context that were re-run that way / that failed on both structures.  (vilsolve_debug.h has the hook that loses a flag on purpose.) */
+int vil_recovery_counts(vil_ctx* ctx, int64_t* recovered, int64_t* failed);
+
 /* kernel timing with HIP events recorded on the library's own stream around every sweep launch
  * (bench.py's roofline leg).  Off by default. */
 typedef struct vil_profile {
@@ -355,19 +322,11 @@ typedef struct vil_profile {
     double reduce_ms;              /* of which: sweep end -> reduce end                         */
     double collective_ms;          /* of which: reduce end -> end of the iteration's collective (sharded solves; ~0 otherwise) */
 } vil_profile;
-int vil_profile_enable(vil_ctx* ctx, int on);
-int vil_profile_read(vil_ctx* ctx, vil_profile* out, int reset);
 /* One-launch iterations (the whole trust-region iteration as one kernel launch: sweep, gather, chain elimination, step): the launch stamps its phases with the
  * device's 100 MHz wall clock while profiling is on -- vil_profile.sweep_ms is then the sweep PHASE (first workgroup started -> last sweep role's record out),
- * reduce_ms the gather's tail behind it, step_ms the rest of the launch.  vil_profile_phases returns the average position in microseconds of 16 phase stamps
- * after the launch's first workgroup started (24 slots; csrc/vilsolve.hip lists them) and the number of launches averaged. */
-int vil_profile_phases(vil_ctx* ctx, double* avg_us32, int64_t* launches, int reset);
-/* the raw stamps (100 MHz device clock; 32 per launch / iteration, slot 0 stored inverted; 0: not stamped) of the last profiled solve: returns the launches copied */
-int vil_debug_read_stamps(vil_ctx* ctx, uint64_t* out, int32_t max_launches);
-/* the 16 wall-clock stamps (100 MHz) the kernels of the context's LAST marginalisation left: k_marg [0] entered, [1] dropped block gathered, [2] its Cholesky inverse
- * done, [3] kept x dropped blocks staged, [4] T = A_kd A_dd^-1, [5] A = A_kk - T A_dk and b, [6] symmetrised copies out; k_marg_fast [7] entered, [8] tiles loaded,
- * [9] n x n factorisation done, [10] J0 / r0 out; k_marg (pivoted square root, only when the un-pivoted one was refused) [11] entered, [12] done */
-int vil_debug_marg_stamps(vil_ctx* ctx, uint64_t* out16);
+ * reduce_ms the gather's tail behind it, step_ms the rest of the launch.  The stamps themselves, by phase and by workgroup: vilsolve_debug.h. */
+int vil_profile_enable(vil_ctx* ctx, int on);
+int vil_profile_read(vil_ctx* ctx, vil_profile* out, int reset);
 
 /* replaces ceres::CostFunction::Evaluate for a whole factor class at once: raw (no loss) residuals
  * and row-major global-size Jacobian blocks, factor-major, in the caller's factor order. */

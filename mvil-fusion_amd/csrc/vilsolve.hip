@@ -1,4 +1,4 @@
-// libvilsolve.so -- C-ABI (include/vilsolve.h) over the gfx950 kernels.
+// libvilsolve.so -- C-ABI (include/vilsolve.h; its lab bench: include/vilsolve_debug.h) over the gfx950 kernels.
 // Replaces, for mVIL-Fusion's Estimator::optimization() (estimator.cpp:1124-1687), the ceres::Problem
 // construction + ceres::Solve + MarginalizationInfo machinery.  No CPU fallback: every compute entry
 // point needs a HIP device and returns VIL_ERR_DEVICE otherwise.
@@ -22,7 +22,7 @@
 #include <rccl/rccl.h>   // types only: RCCL is bound at run time (dlopen) so that a process which already
                          // carries an RCCL (PyTorch bundles one) never ends up with two copies
 
-#include "../../include/vilsolve.h"
+#include "../../include/vilsolve_debug.h"
 #include "vil_internal.h"
 #include "vil_tuning.hpp"
 #include "vil_coop.hpp"
@@ -1617,43 +1617,10 @@ int vil_profile_enable(vil_ctx* c, int on) {
     c->stamps = on == 2;          // 2: the phase stamps alone -- the launch structure stays the library's choice (the persistent solve keeps its one launch; no events)
     return VIL_OK;
 }
-/* average position (us after the launch's first workgroup started) of the phase stamps of the one-launch iterations timed since the last reset:
- * [0] 0, [1] last visual / LiDAR / ICP-LPS role done, [2] last IMU role done, [3] chain: records seen, [4] chain: W^T complete, [5] last gather workgroup done,
- * [6] last gather workgroup saw the visual flags, [7] master started, [8] master saw the gather's flags, [9] master saw the W W^T tiles,
- * [10] dense factorisation done, [11] x_p published, [12] master done, [13] last tile workgroup done, [14] chain: its part of S' gathered, [15] prior role done,
- * [16 .. 20] IMU role of factor 0: entered, inputs staged, raw blocks done, whitened, record stores issued; [21 .. 23] master: chain back-substituted (solve done),
- * step vectors + helpers' sums in, candidate formed */
-int vil_profile_phases(vil_ctx* c, double* avg_us, int64_t* launches, int reset) {
-    if (!c || !avg_us) return VIL_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < VIL_PROF_SLOTS; ++k) avg_us[k] = c->phase_n ? c->phase_us[k] / (double)c->phase_n : 0.0;
-    avg_us[0] = c->period_n ? c->phase_us[0] / (double)c->period_n : 0.0;      // [0]: average iteration period inside a persistent solve (0: launches)
-    if (launches) *launches = c->phase_n;
-    if (reset) { for (double& v : c->phase_us) v = 0.0; c->phase_n = 0; c->period_n = 0; }
-    return VIL_OK;
-}
 int vil_profile_read(vil_ctx* c, vil_profile* out, int reset) {
     if (!c || !out) return VIL_ERR_INVALID_ARGUMENT;
     *out = c->prof;
     if (reset) c->prof = vil_profile{0, 0.0, 0, 0.0, 0.0, 0.0};
-    return VIL_OK;
-}
-
-int vil_debug_read_stamps(vil_ctx* c, uint64_t* out, int32_t max_launches) {
-    if (!c || !out || max_launches < 0) return VIL_ERR_INVALID_ARGUMENT;
-    const size_t n = std::min((size_t)max_launches * VIL_PROF_SLOTS, c->last_stamps.size());
-    for (size_t i = 0; i < n; ++i) out[i] = c->last_stamps[i];
-    return (int)(n / VIL_PROF_SLOTS);
-}
-int vil_debug_marg_stamps(vil_ctx* c, uint64_t* out16) {
-    if (!c || !out16 || !c->d_marg_ts) return VIL_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out16, c->d_marg_ts, 8 * 16, hipMemcpyDeviceToHost));
-    return VIL_OK;
-}
-int vil_debug_read(vil_ctx* c, long long* out64) {
-    if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipMemcpy(out64, c->P.dbg, 8 * 64, hipMemcpyDeviceToHost));
     return VIL_OK;
 }
 
@@ -1669,21 +1636,18 @@ int vil_reset_state(vil_ctx* c) {
 static int top_rung(const vil_ctx* c) {
     return !c->ls.fused || c->split ? 2 : (c->ls.persist && !c->profiling ? 0 : 1);
 }
-// One attempt at the solve on rung `rung` of the ladder (top_rung).
-// *gave_up: a wait inside a launch gave up (status -2 from the master, or no launch ever reported `done`): the caller decides about the retry.
-static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, const std::chrono::steady_clock::time_point t0, const bool direct, const int rung, bool* gave_up) {
-    const SolveOpts so = to_dev_opts(o);
-    c->mirror_state = false;
-    *gave_up = false;
-    const bool persist = rung == 0, fused = rung <= 1;
-    int st = init_ctl(c, o, 0);
-    if (st != VIL_OK) return st;
-    if ((c->profiling || (c->stamps && persist)) && fused && c->d_prof) HIPCHK(hipMemsetAsync(c->d_prof, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
-    // every iteration = sweep + gather + step kernel; `done` turns the tail of a chunk into no-ops, and the first sweep launch that finds
-    // the solve finished writes the result out (vil_finish.hpp); k_finish at the end of every chunk covers a solve that ends in its last iteration
-    bool finished = false, polled_done = false;
-    // iterations are enqueued in chunks without host round trips; the first chunk is sized by the previous solve of
-    // this context (consecutive windows of a tracker need similar iteration counts), later chunks are short
+
+// ---- one attempt at a solve, stage by stage: solve_attempt (below them) reads top to bottom ----------------------------------------------------
+// What an attempt runs, by value: the options and their device form, the start of the solve on the host clock, the rung of the ladder (top_rung), no graph replay
+struct Attempt {
+    vil_options o; SolveOpts so; std::chrono::steady_clock::time_point t0; int rung; bool direct;
+    bool persist() const { return rung == 0; }
+    bool fused() const { return rung <= 1; }
+    double elapsed_s() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
+// iterations are enqueued in chunks without host round trips; the first chunk is sized by the previous solve of
+// this context (consecutive windows of a tracker need similar iteration counts), later chunks are short
+static int first_chunk(const vil_ctx* c, bool fused) {
     int chunk = std::min(15, std::max(3, c->last_live));
     // One-launch iterations write the result out themselves as soon as a launch finds the solve finished (vil_iter.hpp): a chunk that is too LONG costs the stream
     // ~5 us per dead launch and the host nothing, one that is too SHORT costs a host round trip (~70 us) and a second chunk.  The first solve of an upload -- what a
@@ -1691,166 +1655,218 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
     // re-solves of one upload (graph replay, the same count again and again) keep the exact size.
     if (fused && c->solves_since_upload == 0) { int mx = 3; for (int v : c->recent_live) mx = std::max(mx, v); chunk = std::min(VIL_MAX_CHUNK, mx + 2); }
     if (c->profiling) chunk = std::min(chunk, (int)c->ev.size() / 2 - 1);      // (events bracket every launch of a chunk: ev[2 q], ev[2 q + 1], ev[2 launched])
-    for (int it = 0; it <= o->max_iterations + 8 && !finished; chunk = 3) {
-        int launched = 0;
-        const int sweeps_before = (it == 0) ? 0 : c->h_ctl->n_sweeps;
-        // Repeated solves of ONE upload (bench, re-solves after a rejected frame) replay a captured hipGraph of the chunk:
-        // ~2 % less inter-kernel gap.  The first solve of an upload launches directly -- capturing costs more than it saves.
-        if (c->use_graph < 0) { const char* ev = VIL_TUNE_ENV("VIL_GRAPH"); c->use_graph = ev ? atoi(ev) : 1; }
-        const int nthis = std::min(chunk, o->max_iterations + 9 - it);
-        // hipGraph replay: un-sharded solves, and sharded ones whose collective is the library's own kernels (peer-buffer exchange).  RCCL calls are
-        // launched directly (whether a given RCCL build captures correctly is not something this path bets the multi-GPU run on); the in-process
-        // communicator synchronises on the host.  Polling the finished solve's mirror works for everything that is in stream order.
-        const bool no_graph = c->split && !c->ipc;
-        if (c->use_graph && c->solves_since_upload > 0 && !c->profiling && !no_graph && !c->graph_failed && !direct && !persist && nthis > 0) {      // (direct: a retry, or a solve with a debug hook in its parameter block)
-            hipGraphExec_t exec = nullptr;
-            for (auto& g : c->graphs) if (g.n == nthis && memcmp(&g.so, &so, sizeof so) == 0) exec = g.exec;
-            if (!exec) {
-                hipGraph_t graph = nullptr;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                int cst = VIL_OK;
-                for (int q = 0; q < nthis && cst == VIL_OK; ++q) { if (fused) cst = launch_iter(c, so); else { launch_sweep(c, so); cst = launch_reduce_step(c, so, true, nullptr); } }
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);
-                const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-                const bool forced = c->fail_capture > 0;
-                if (forced) --c->fail_capture;
-                if (cst != VIL_OK || ce != hipSuccess || forced || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-                    // a chunk that cannot be captured or instantiated (a collective the RCCL build at hand does not capture, a driver out of graph memory): nothing has
-                    // run yet, so THIS solve and every later one of the context take the direct launches right below -- the caller (optimization()) has no retry
-                    (void)hipGetLastError();
-                    if (graph) hipGraphDestroy(graph);
-                    exec = nullptr; c->graph_failed = true;
-                    // (a capture that could not be ENDED may leave the stream in an invalidated capture state: the direct launches below would fail the same way.
-                    //  The collectives advance no host-side state while captured -- the peer-buffer exchange counts in device memory, when its kernels run)
-                    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                    if (ce != hipSuccess && (hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) { (void)hipGetLastError(); return VIL_ERR_DEVICE; }
-                } else {
-                    hipGraphDestroy(graph);
-                    c->graphs.push_back({nthis, so, exec});
-                }
-            }
-            if (exec) { HIPCHK(hipGraphLaunch(exec, c->stream)); it += nthis; launched = nthis; }
-        }
-        if (launched == 0 && persist) {
-            // ONE launch runs every iteration and writes the result out; the time cap travels with it (the master reads the device clock where ceres reads its own)
-            long long ticks = 0;
-            if (o->max_time_s > 0) ticks = std::max(1LL, (long long)((o->max_time_s - std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()) * 1e8));
-            if (c->stamps && !c->ev.empty()) HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            st = launch_solve(c, so, ticks);
-            if (st != VIL_OK) return st;
-            if (c->stamps && !c->ev.empty()) HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            launched = 1; it = o->max_iterations + 9;
-        }
-        if (launched == 0) {
-            for (int q = 0; q < chunk && it <= o->max_iterations + 8; ++q, ++it, ++launched) {
-                if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q], c->stream));
-                if (fused) {
-                    // (one launch: the events bracket the whole iteration; what the sweep roles took inside it comes from the launch's own clock stamps, below)
-                    st = launch_iter(c, so);
-                    if (st != VIL_OK) return st;
-                    continue;
-                }
-                launch_sweep(c, so);
-                if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q + 1], c->stream));
-                st = launch_reduce_step(c, so, true, c->profiling ? c->ev_mid[q] : nullptr, c->profiling ? c->ev_coll[q] : nullptr);
-                if (st != VIL_OK) return st;          // a failed collective fails on every rank (all_reduce): nobody is left waiting
-            }
-            if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * launched], c->stream));
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);      // the write-out of a solve that ended in the chunk's last iteration
-        }
-        // solve_finish leaves Ctl, the final state and then the solve generation in pinned host memory: poll that word instead of
-        // synchronising (the no-op tail of the chunk is not waited for, nothing is copied afterwards).  A chunk that runs out without
-        // finishing is seen by hipStreamQuery and takes the copy + synchronise route, as do profiling and multi-rank solves.
-        bool polled = false;
-        if (c->d_hseq && !c->profiling && !(c->split && c->lcomm != nullptr)) {
-            volatile int* seq = (volatile int*)(c->h_mirror + sizeof(Ctl));
-            const int gen = c->solve_gen;
-            const auto tp0 = std::chrono::steady_clock::now();
-            for (long spin = 1;; ++spin) {
-                if (*seq == gen) { polled = true; break; }
-                if ((spin & 0x3ff) == 0) {
-                    const hipError_t q = hipStreamQuery(c->stream);
-                    if (q == hipSuccess) { polled = *seq == gen; break; }
-                    if (q != hipErrorNotReady) return VIL_ERR_DEVICE;
-                    if (std::chrono::steady_clock::now() - tp0 > std::chrono::seconds(2)) break;
-                }
-            }
-            if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_ctl, c->h_mirror, sizeof(Ctl)); polled_done = true; }
-        }
-        if (!polled) {
-            HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-        finished = c->h_ctl->done != 0;
-        if (c->profiling) {
-            int live = c->h_ctl->n_sweeps - sweeps_before;   // launches that found done == 0
-            live = std::max(0, std::min(live, launched));
-            for (int q = 0; q < live; ++q) {
-                float ms = 0.f;
-                if (fused) {      // one launch: the events give its whole duration (to step_ms; the sweep phase's share moves to sweep_ms from the launch's own stamps, below)
-                    HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q], c->ev[2 * q + 2])); c->prof.step_ms += ms; c->prof.sweep_launches++; c->prof.step_launches++;
-                    continue;
-                }
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q], c->ev[2 * q + 1])); c->prof.sweep_ms += ms; c->prof.sweep_launches++;
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q + 1], c->ev[2 * q + 2])); c->prof.step_ms += ms; c->prof.step_launches++;
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q + 1], c->ev_mid[q])); c->prof.reduce_ms += ms;
-                HIPCHK(hipEventElapsedTime(&ms, c->ev_mid[q], c->ev_coll[q])); c->prof.collective_ms += ms;
-            }
-        }
-        // (sharded solves ignore the host-timed cap: the ranks' clocks disagree, and a rank that stops enqueuing chunks leaves its peers waiting in
-        //  the collective of the next iteration -- the iteration cap is the bound every rank applies identically)
-        if (!finished && !c->split && o->max_time_s > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= o->max_time_s) {
-            // ceres max_solver_time_in_seconds (estimator.cpp:1411): the host ends the solve; the accepted state is written out on request
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, c->P, (int)VIL_TERM_MAX_TIME);
-            HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            finished = true; polled_done = false;
-        }
+    return chunk;
+}
+// Repeated solves of ONE upload (bench, re-solves after a rejected frame) replay a captured hipGraph of the chunk:
+// ~2 % less inter-kernel gap.  The first solve of an upload launches directly -- capturing costs more than it saves.
+// hipGraph replay: un-sharded solves, and sharded ones whose collective is the library's own kernels (peer-buffer exchange).  RCCL calls are
+// launched directly (whether a given RCCL build captures correctly is not something this path bets the multi-GPU run on); the in-process
+// communicator synchronises on the host.  Polling the finished solve's mirror works for everything that is in stream order.
+static bool may_replay(vil_ctx* c, const Attempt& a) {
+    if (c->use_graph < 0) { const char* ev = VIL_TUNE_ENV("VIL_GRAPH"); c->use_graph = ev ? atoi(ev) : 1; }
+    const bool no_graph = c->split && !c->ipc;
+    return c->use_graph && c->solves_since_upload > 0 && !c->profiling && !no_graph && !a.direct && !a.persist();      // (direct: a retry, or a solve with a debug hook in its parameter block)
+}
+// The hipGraph of a chunk of n iterations and its k_finish: the cached one of this (n, options), or a fresh capture.  *exec == nullptr: launch directly
+static int chunk_graph(vil_ctx* c, const Attempt& a, int n, hipGraphExec_t* exec) {
+    *exec = nullptr;
+    if (c->graph_failed) return VIL_OK;
+    for (auto& g : c->graphs) if (g.n == n && memcmp(&g.so, &a.so, sizeof a.so) == 0) *exec = g.exec;
+    if (*exec) return VIL_OK;
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    int cst = VIL_OK;
+    for (int q = 0; q < n && cst == VIL_OK; ++q) { if (a.fused()) cst = launch_iter(c, a.so); else { launch_sweep(c, a.so); cst = launch_reduce_step(c, a.so, true, nullptr); } }
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);
+    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
+    const bool forced = c->fail_capture > 0;
+    if (forced) --c->fail_capture;
+    if (cst != VIL_OK || ce != hipSuccess || forced || hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        // a chunk that cannot be captured or instantiated (a collective the RCCL build at hand does not capture, a driver out of graph memory): nothing has
+        // run yet, so THIS solve and every later one of the context take the direct launches (enqueue_chunk) -- the caller (optimization()) has no retry
+        (void)hipGetLastError();
+        if (graph) hipGraphDestroy(graph);
+        *exec = nullptr; c->graph_failed = true;
+        // (a capture that could not be ENDED may leave the stream in an invalidated capture state: the direct launches would fail the same way.
+        //  The collectives advance no host-side state while captured -- the peer-buffer exchange counts in device memory, when its kernels run)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (ce != hipSuccess && (hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) { (void)hipGetLastError(); return VIL_ERR_DEVICE; }
+    } else {
+        hipGraphDestroy(graph);
+        c->graphs.push_back({n, a.so, *exec});
     }
-    HIPCHK(hipGetLastError());
+    return VIL_OK;
+}
+// The three ways a pass puts iterations on the stream.  Each returns how many (> 0), or a status (< 0).
+static int enqueue_replay(vil_ctx* c, hipGraphExec_t exec, int n) {
+    HIPCHK(hipGraphLaunch(exec, c->stream));
+    return n;
+}
+static int enqueue_resident(vil_ctx* c, const Attempt& a, int left) {
+    // ONE launch runs every iteration and writes the result out; the time cap travels with it (the master reads the device clock where ceres reads its own)
+    long long ticks = 0;
+    if (a.o.max_time_s > 0) ticks = std::max(1LL, (long long)((a.o.max_time_s - a.elapsed_s()) * 1e8));
+    if (c->stamps && !c->ev.empty()) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    const int st = launch_solve(c, a.so, ticks);
+    if (st != VIL_OK) return st;
+    if (c->stamps && !c->ev.empty()) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    return left;      // every iteration the solve has left
+}
+static int enqueue_chunk(vil_ctx* c, const Attempt& a, int n) {
+    for (int q = 0; q < n; ++q) {
+        if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q], c->stream));
+        if (a.fused()) {
+            // (one launch: the events bracket the whole iteration; what the sweep roles took inside it comes from the launch's own clock stamps: account_stamps)
+            const int st = launch_iter(c, a.so);
+            if (st != VIL_OK) return st;
+            continue;
+        }
+        launch_sweep(c, a.so);
+        if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q + 1], c->stream));
+        const int st = launch_reduce_step(c, a.so, true, c->profiling ? c->ev_mid[q] : nullptr, c->profiling ? c->ev_coll[q] : nullptr);
+        if (st != VIL_OK) return st;          // a failed collective fails on every rank (all_reduce): nobody is left waiting
+    }
+    if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * n], c->stream));
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);      // the write-out of a solve that ended in the chunk's last iteration
+    return n;
+}
+// solve_finish leaves Ctl, the final state and then the solve generation in pinned host memory: poll that word instead of
+// synchronising (the no-op tail of the chunk is not waited for, nothing is copied afterwards).  A chunk that runs out without
+// finishing is seen by hipStreamQuery and takes the copy + synchronise route, as do profiling and multi-rank solves.
+// Leaves *c->h_ctl filled; *via_mirror is set when it came through the mirror.
+static int await_result(vil_ctx* c, bool* via_mirror) {
+    bool polled = false;
+    if (c->d_hseq && !c->profiling && !(c->split && c->lcomm != nullptr)) {
+        volatile int* seq = (volatile int*)(c->h_mirror + sizeof(Ctl));
+        const int gen = c->solve_gen;
+        const auto tp0 = std::chrono::steady_clock::now();
+        for (long spin = 1;; ++spin) {
+            if (*seq == gen) { polled = true; break; }
+            if ((spin & 0x3ff) == 0) {
+                const hipError_t q = hipStreamQuery(c->stream);
+                if (q == hipSuccess) { polled = *seq == gen; break; }
+                if (q != hipErrorNotReady) return VIL_ERR_DEVICE;
+                if (std::chrono::steady_clock::now() - tp0 > std::chrono::seconds(2)) break;
+            }
+        }
+        if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_ctl, c->h_mirror, sizeof(Ctl)); *via_mirror = true; }
+    }
+    if (!polled) {
+        HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return VIL_OK;
+}
+// profiling: the HIP events of a chunk of `launched` direct launches, for those of them that found the solve unfinished
+static int account_events(vil_ctx* c, bool fused, int launched, int sweeps_before) {
+    int live = c->h_ctl->n_sweeps - sweeps_before;   // launches that found done == 0
+    live = std::max(0, std::min(live, launched));
+    for (int q = 0; q < live; ++q) {
+        float ms = 0.f;
+        if (fused) {      // one launch: the events give its whole duration (to step_ms; the sweep phase's share moves to sweep_ms from the launch's own stamps: account_stamps)
+            HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q], c->ev[2 * q + 2])); c->prof.step_ms += ms; c->prof.sweep_launches++; c->prof.step_launches++;
+            continue;
+        }
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q], c->ev[2 * q + 1])); c->prof.sweep_ms += ms; c->prof.sweep_launches++;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q + 1], c->ev[2 * q + 2])); c->prof.step_ms += ms; c->prof.step_launches++;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[2 * q + 1], c->ev_mid[q])); c->prof.reduce_ms += ms;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev_mid[q], c->ev_coll[q])); c->prof.collective_ms += ms;
+    }
+    return VIL_OK;
+}
+// (sharded solves ignore the host-timed cap: the ranks' clocks disagree, and a rank that stops enqueuing chunks leaves its peers waiting in
+//  the collective of the next iteration -- the iteration cap is the bound every rank applies identically)
+static bool host_cap_reached(const vil_ctx* c, const Attempt& a) {
+    return !c->split && a.o.max_time_s > 0 && a.elapsed_s() >= a.o.max_time_s;
+}
+// ceres max_solver_time_in_seconds (estimator.cpp:1411): the host ends the solve; the accepted state is written out on request
+static int finish_at_cap(vil_ctx* c) {
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, c->P, (int)VIL_TERM_MAX_TIME);
+    HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VIL_OK;
+}
+// the launches' own clock stamps (100 MHz): the sweep phase of a one-launch iteration = first workgroup started -> last sweep role posted
+static int account_stamps(vil_ctx* c, bool persist, int n_sweeps) {
+    std::vector<unsigned long long>& hp = c->last_stamps; hp.assign((size_t)64 * VIL_PROF_SLOTS, 0ull);
+    HIPCHK(hipMemcpyAsync(hp.data(), c->d_prof, 8 * hp.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (persist && c->stamps && !c->ev.empty()) {      // the resident launch as a whole (HIP events on the library's stream): step_ms / step_launches; its iterations: sweep_launches
+        float ms = 0.f;
+        HIPCHK(hipEventSynchronize(c->ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        c->prof.step_ms += ms; c->prof.step_launches++; c->prof.sweep_launches += n_sweeps;
+    }
+    for (int q = 0; q < n_sweeps; ++q) {
+        const unsigned long long* r = hp.data() + (size_t)q * VIL_PROF_SLOTS;
+        if (!r[0] || !r[1]) continue;
+        const unsigned long long t0 = ~r[0];
+        // the phase table describes a FULL iteration (linearisation, dense solve, step): the last launch of a solve judges a candidate and ends -- averaged in,
+        // as until round 5, it pulled every late stamp ~10 % towards zero ("master done 50.3 us" was 55.7)
+        if (r[10] >= t0 && r[12] >= t0) {
+            for (int k = 1; k < VIL_PROF_SLOTS; ++k) if (r[k] >= t0) c->phase_us[k] += (double)(r[k] - t0) * 0.01;
+            c->phase_n++;
+            if (q + 1 < n_sweeps && r[VIL_PROF_SLOTS]) { c->phase_us[0] += (double)(~r[VIL_PROF_SLOTS] - t0) * 0.01; c->period_n++; }      // (persistent solve: first role of this iteration -> first role of the next)
+        }
+        const double sweep_us = (double)(r[1] - t0) * 0.01, gather_us = r[5] > r[1] ? (double)(r[5] - r[1]) * 0.01 : 0.0;
+        c->prof.sweep_ms += sweep_us * 1e-3; c->prof.step_ms -= sweep_us * 1e-3; c->prof.reduce_ms += gather_us * 1e-3;      // (the events gave the whole launch to step_ms)
+    }
+    return VIL_OK;
+}
+// Ctl -> vil_summary, the history that sizes the next solve's first chunk, and the status of the attempt
+static int summarize(vil_ctx* c, const Attempt& a, bool via_mirror, vil_summary* sum) {
     const Ctl& ctl = *c->h_ctl;
-    // a wait inside a launch gave up (vil_math.hpp, spin_until_eq): the master ended the solve with status -2 -- or never ran, and the launches drained without a `done`
-    if (!finished || ctl.status == VIL_ERR_DEVICE) { *gave_up = true; return VIL_ERR_DEVICE; }
     c->solves_since_upload++;
     c->last_live = ctl.n_sweeps;
     c->recent_live[c->recent_at++ & 7] = ctl.n_sweeps;
-    if ((c->profiling || (c->stamps && persist)) && fused && c->d_prof && ctl.n_sweeps <= 64) {
-        // the launches' own clock stamps (100 MHz): the sweep phase of a one-launch iteration = first workgroup started -> last sweep role posted
-        std::vector<unsigned long long>& hp = c->last_stamps; hp.assign((size_t)64 * VIL_PROF_SLOTS, 0ull);
-        HIPCHK(hipMemcpyAsync(hp.data(), c->d_prof, 8 * hp.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (persist && c->stamps && !c->ev.empty()) {      // the resident launch as a whole (HIP events on the library's stream): step_ms / step_launches; its iterations: sweep_launches
-            float ms = 0.f;
-            HIPCHK(hipEventSynchronize(c->ev[1]));
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            c->prof.step_ms += ms; c->prof.step_launches++; c->prof.sweep_launches += ctl.n_sweeps;
-        }
-        for (int q = 0; q < ctl.n_sweeps; ++q) {
-            const unsigned long long* r = hp.data() + (size_t)q * VIL_PROF_SLOTS;
-            if (!r[0] || !r[1]) continue;
-            const unsigned long long t0 = ~r[0];
-            // the phase table describes a FULL iteration (linearisation, dense solve, step): the last launch of a solve judges a candidate and ends -- averaged in,
-            // as until round 5, it pulled every late stamp ~10 % towards zero ("master done 50.3 us" was 55.7)
-            if (r[10] >= t0 && r[12] >= t0) {
-                for (int k = 1; k < VIL_PROF_SLOTS; ++k) if (r[k] >= t0) c->phase_us[k] += (double)(r[k] - t0) * 0.01;
-                c->phase_n++;
-                if (q + 1 < ctl.n_sweeps && r[VIL_PROF_SLOTS]) { c->phase_us[0] += (double)(~r[VIL_PROF_SLOTS] - t0) * 0.01; c->period_n++; }      // (persistent solve: first role of this iteration -> first role of the next)
-            }
-            const double sweep_us = (double)(r[1] - t0) * 0.01, gather_us = r[5] > r[1] ? (double)(r[5] - r[1]) * 0.01 : 0.0;
-            c->prof.sweep_ms += sweep_us * 1e-3; c->prof.step_ms -= sweep_us * 1e-3; c->prof.reduce_ms += gather_us * 1e-3;      // (the events gave the whole launch to step_ms)
-        }
-    }
     memset(sum, 0, sizeof *sum);
     sum->iterations = ctl.iter; sum->successful_steps = ctl.nsucc; sum->termination = ctl.term;
     sum->initial_cost = ctl.initial_cost; sum->final_cost = ctl.cost_cur;
     for (int i = 0; i < VIL_MAX_TRACE; ++i) { sum->cost_trace[i] = ctl.cost_trace[i]; sum->radius_trace[i] = ctl.radius_trace[i]; }
-    sum->t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sum->t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a.t0).count();
     // (the accepted state is x[0] = x[1] on the device, gauge-fixed when asked for: solve_finish ran in stream order; whoever reads the
     //  window afterwards orders itself behind it on the stream)
-    c->mirror_state = polled_done && c->d_hstate != nullptr;
+    c->mirror_state = via_mirror && c->d_hstate != nullptr;
     if (ctl.status != 0) return ctl.status;
     if (!std::isfinite(ctl.cost_cur)) return VIL_ERR_NON_FINITE;
     return VIL_OK;
+}
+// One attempt at the solve on rung `rung` of the ladder (top_rung).
+// *gave_up: a wait inside a launch gave up (status -2 from the master, or no launch ever reported `done`): the caller decides about the retry.
+static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, const std::chrono::steady_clock::time_point t0, const bool direct, const int rung, bool* gave_up) {
+    const Attempt a = {*o, to_dev_opts(o), t0, rung, direct};
+    c->mirror_state = false;
+    *gave_up = false;
+    int st = init_ctl(c, o, 0);
+    if (st != VIL_OK) return st;
+    const bool stamped = (c->profiling || (c->stamps && a.persist())) && a.fused() && c->d_prof != nullptr;      // the launches leave their own clock stamps in d_prof
+    if (stamped) HIPCHK(hipMemsetAsync(c->d_prof, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
+    // every iteration = sweep + gather + step kernel; `done` turns the tail of a chunk into no-ops, and the first sweep launch that finds
+    // the solve finished writes the result out (vil_finish.hpp); k_finish at the end of every chunk covers a solve that ends in its last iteration
+    bool finished = false, via_mirror = false;
+    int chunk = first_chunk(c, a.fused());
+    for (int it = 0; it <= o->max_iterations + 8 && !finished; chunk = 3) {
+        const int sweeps_before = (it == 0) ? 0 : c->h_ctl->n_sweeps;
+        const int left = o->max_iterations + 9 - it, nthis = std::min(chunk, left);
+        hipGraphExec_t exec = nullptr;
+        if (may_replay(c, a)) { st = chunk_graph(c, a, nthis, &exec); if (st != VIL_OK) return st; }
+        int n;      // iterations this pass puts on the stream (< 0: a status)
+        if (exec) n = enqueue_replay(c, exec, nthis);
+        else if (a.persist()) n = enqueue_resident(c, a, left);
+        else n = enqueue_chunk(c, a, nthis);
+        if (n < 0) return n;
+        it += n;
+        st = await_result(c, &via_mirror);
+        if (st != VIL_OK) return st;
+        finished = c->h_ctl->done != 0;
+        if (c->profiling) { st = account_events(c, a.fused(), n, sweeps_before); if (st != VIL_OK) return st; }
+        if (!finished && host_cap_reached(c, a)) { st = finish_at_cap(c); if (st != VIL_OK) return st; finished = true; via_mirror = false; }
+    }
+    HIPCHK(hipGetLastError());
+    // a wait inside a launch gave up (vil_math.hpp, spin_until_eq): the master ended the solve with status -2 -- or never ran, and the launches drained without a `done`
+    if (!finished || c->h_ctl->status == VIL_ERR_DEVICE) { *gave_up = true; return VIL_ERR_DEVICE; }
+    if (stamped && c->h_ctl->n_sweeps <= 64) { st = account_stamps(c, a.persist(), c->h_ctl->n_sweeps); if (st != VIL_OK) return st; }
+    return summarize(c, a, via_mirror, sum);
 }
 
 int vil_solve_resident(vil_ctx* c, const vil_options* o, vil_summary* sum) {
@@ -1950,11 +1966,6 @@ int vil_solve_batch(vil_ctx** ctxs, int32_t n, const vil_options* o, vil_summary
     return VIL_OK;
 }
 
-int vil_debug_drop_flag(vil_ctx* c, int32_t role, int32_t launch) {
-    if (!c || launch < 0) return VIL_ERR_INVALID_ARGUMENT;
-    c->drop_role = role; c->drop_launch = launch;
-    return VIL_OK;
-}
 int vil_recovery_counts(vil_ctx* c, int64_t* recovered, int64_t* failed) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     if (recovered) *recovered = c->n_recovered;
@@ -2373,8 +2384,6 @@ int vil_comm_message_bytes(vil_ctx* c, int64_t* bytes_per_peer, int64_t* bytes_f
 }
 
 // ---- window residency across frames (include/vilsolve.h) ------------------------------------------------------------------------
-int vil_debug_fail_graph_capture(vil_ctx* c, int32_t n) { if (!c || n < 0) return VIL_ERR_INVALID_ARGUMENT; c->fail_capture = n; c->graph_failed = false; return VIL_OK; }
-int vil_debug_set_launch_mode(vil_ctx* c, int32_t mode) { if (!c || mode < 0 || mode > 4) return VIL_ERR_INVALID_ARGUMENT; c->launch_mode = mode; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
 int vil_comm_info(vil_ctx* c, int32_t* rank, int32_t* world, int32_t* transport) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     if (rank) *rank = c->rank;
@@ -2382,48 +2391,6 @@ int vil_comm_info(vil_ctx* c, int32_t* rank, int32_t* world, int32_t* transport)
     if (transport) *transport = c->comm ? 1 : (c->lcomm ? 2 : (c->ipc ? (c->ipc->ready ? 3 : -3) : 0));
     return VIL_OK;
 }
-int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) {
-    if (!c || !A || !L || !x || !ok || D < 1 || D > 159 || variant < 0 || variant > 1) return VIL_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(c->device));
-    const int R = D + 1, T = (R + 15) / 16, nt = T * (T + 1) / 2;
-    const size_t lds = 8 * (size_t)TILE_SZ * nt, nb = 8 * (size_t)R * R;
-    double *dA = nullptr, *dL = nullptr, *dx = nullptr; int* dok = nullptr;
-    HIPCHK(hipMalloc((void**)&dA, nb)); HIPCHK(hipMalloc((void**)&dL, nb)); HIPCHK(hipMalloc((void**)&dx, 8 * (size_t)R)); HIPCHK(hipMalloc((void**)&dok, 64));
-    HIPCHK(hipMemcpy(dA, A, nb, hipMemcpyHostToDevice));
-    const bool small = nt <= 18;                         // (three register tiles per tile wave are enough -- what the step takes at K <= 10)
-    const void* fn = variant ? (small ? (const void*)k_debug_dense<3, true> : (const void*)k_debug_dense<CH_SLOTS, true>) : (small ? (const void*)k_debug_dense<3, false> : (const void*)k_debug_dense<CH_SLOTS, false>);
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* args[] = {(void*)&dA, (void*)&dL, (void*)&dx, (void*)&dok, (void*)&D};
-    HIPCHK(hipLaunchKernel(fn, dim3(1), dim3(VIL_STEP_THREADS), args, lds, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int hok = 0;
-    HIPCHK(hipMemcpy(L, dL, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(x, dx, 8 * (size_t)D, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hok, dok, 4, hipMemcpyDeviceToHost));
-    *ok = hok;
-    hipFree(dA); hipFree(dL); hipFree(dx); hipFree(dok);
-    return VIL_OK;
-}
-int vil_profile_workgroups(vil_ctx* c, int32_t launch, uint64_t* times, int32_t max_workgroups) {
-    if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    if (!times) {                                         // arm: the solves from now on record launch `launch` (< 0: none)
-        c->wg_launch = launch;
-        if (c->d_prof) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMemset((char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 0, 8 * 2 * VIL_PROF_WGS)); }
-        return VIL_OK;
-    }
-    if (!c->d_prof || max_workgroups < 0) return VIL_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const int n = std::min<int>(max_workgroups, VIL_PROF_WGS);
-    HIPCHK(hipMemcpy(times, (char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 8 * 2 * (size_t)n, hipMemcpyDeviceToHost));
-    return VIL_OK;
-}
-int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->slim_emul = on != 0; return VIL_OK; }
-int vil_debug_get_launch_structure(vil_ctx* c, int32_t* launches_per_iteration, int32_t* one_launch) {
-    if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
-    const int rung = top_rung(c);
-    if (launches_per_iteration) *launches_per_iteration = rung < 2 ? rung : (c->ls.rs_merged != 0 && !c->split ? 2 : 3);      // 0: the whole solve is one resident launch (k_solve)
-    if (one_launch) *one_launch = rung < 2 ? 1 : 0;
-    return VIL_OK;
-}
-int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
 int vil_set_gauge_fix(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->gauge_on = on != 0; return VIL_OK; }      // (takes effect in the next solve)
 
 int vil_lidar_reset(vil_ctx* c) {
@@ -2862,6 +2829,89 @@ int vil_comm_init_local(vil_ctx** ctxs, int n) {
         if (c->comm) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
         c->lcomm = lc; c->rank = r; c->world = n; c->uploaded = false; c->ipc.reset();
     }
+    return VIL_OK;
+}
+
+// ---- the lab bench (include/vilsolve_debug.h): test hooks and the profilers of the kernels' role layout ------------------------------------------
+int vil_debug_set_launch_mode(vil_ctx* c, int32_t mode) { if (!c || mode < 0 || mode > 4) return VIL_ERR_INVALID_ARGUMENT; c->launch_mode = mode; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
+int vil_debug_get_launch_structure(vil_ctx* c, int32_t* launches_per_iteration, int32_t* one_launch) {
+    if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
+    const int rung = top_rung(c);
+    if (launches_per_iteration) *launches_per_iteration = rung < 2 ? rung : (c->ls.rs_merged != 0 && !c->split ? 2 : 3);      // 0: the whole solve is one resident launch (k_solve)
+    if (one_launch) *one_launch = rung < 2 ? 1 : 0;
+    return VIL_OK;
+}
+int vil_debug_fail_graph_capture(vil_ctx* c, int32_t n) { if (!c || n < 0) return VIL_ERR_INVALID_ARGUMENT; c->fail_capture = n; c->graph_failed = false; return VIL_OK; }
+int vil_debug_drop_flag(vil_ctx* c, int32_t role, int32_t launch) {
+    if (!c || launch < 0) return VIL_ERR_INVALID_ARGUMENT;
+    c->drop_role = role; c->drop_launch = launch;
+    return VIL_OK;
+}
+int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
+int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->slim_emul = on != 0; return VIL_OK; }
+int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) {
+    if (!c || !A || !L || !x || !ok || D < 1 || D > 159 || variant < 0 || variant > 1) return VIL_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(c->device));
+    const int R = D + 1, T = (R + 15) / 16, nt = T * (T + 1) / 2;
+    const size_t lds = 8 * (size_t)TILE_SZ * nt, nb = 8 * (size_t)R * R;
+    double *dA = nullptr, *dL = nullptr, *dx = nullptr; int* dok = nullptr;
+    HIPCHK(hipMalloc((void**)&dA, nb)); HIPCHK(hipMalloc((void**)&dL, nb)); HIPCHK(hipMalloc((void**)&dx, 8 * (size_t)R)); HIPCHK(hipMalloc((void**)&dok, 64));
+    HIPCHK(hipMemcpy(dA, A, nb, hipMemcpyHostToDevice));
+    const bool small = nt <= 18;                         // (three register tiles per tile wave are enough -- what the step takes at K <= 10)
+    const void* fn = variant ? (small ? (const void*)k_debug_dense<3, true> : (const void*)k_debug_dense<CH_SLOTS, true>) : (small ? (const void*)k_debug_dense<3, false> : (const void*)k_debug_dense<CH_SLOTS, false>);
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void* args[] = {(void*)&dA, (void*)&dL, (void*)&dx, (void*)&dok, (void*)&D};
+    HIPCHK(hipLaunchKernel(fn, dim3(1), dim3(VIL_STEP_THREADS), args, lds, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int hok = 0;
+    HIPCHK(hipMemcpy(L, dL, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(x, dx, 8 * (size_t)D, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hok, dok, 4, hipMemcpyDeviceToHost));
+    *ok = hok;
+    hipFree(dA); hipFree(dL); hipFree(dx); hipFree(dok);
+    return VIL_OK;
+}
+int vil_debug_read(vil_ctx* c, long long* out64) {
+    if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipMemcpy(out64, c->P.dbg, 8 * 64, hipMemcpyDeviceToHost));
+    return VIL_OK;
+}
+/* average position (us after the launch's first workgroup started) of the phase stamps of the one-launch iterations timed since the last reset:
+ * [0] 0, [1] last visual / LiDAR / ICP-LPS role done, [2] last IMU role done, [3] chain: records seen, [4] chain: W^T complete, [5] last gather workgroup done,
+ * [6] last gather workgroup saw the visual flags, [7] master started, [8] master saw the gather's flags, [9] master saw the W W^T tiles,
+ * [10] dense factorisation done, [11] x_p published, [12] master done, [13] last tile workgroup done, [14] chain: its part of S' gathered, [15] prior role done,
+ * [16 .. 20] IMU role of factor 0: entered, inputs staged, raw blocks done, whitened, record stores issued; [21 .. 23] master: chain back-substituted (solve done),
+ * step vectors + helpers' sums in, candidate formed */
+int vil_profile_phases(vil_ctx* c, double* avg_us, int64_t* launches, int reset) {
+    if (!c || !avg_us) return VIL_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < VIL_PROF_SLOTS; ++k) avg_us[k] = c->phase_n ? c->phase_us[k] / (double)c->phase_n : 0.0;
+    avg_us[0] = c->period_n ? c->phase_us[0] / (double)c->period_n : 0.0;      // [0]: average iteration period inside a persistent solve (0: launches)
+    if (launches) *launches = c->phase_n;
+    if (reset) { for (double& v : c->phase_us) v = 0.0; c->phase_n = 0; c->period_n = 0; }
+    return VIL_OK;
+}
+int vil_profile_workgroups(vil_ctx* c, int32_t launch, uint64_t* times, int32_t max_workgroups) {
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    if (!times) {                                         // arm: the solves from now on record launch `launch` (< 0: none)
+        c->wg_launch = launch;
+        if (c->d_prof) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMemset((char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 0, 8 * 2 * VIL_PROF_WGS)); }
+        return VIL_OK;
+    }
+    if (!c->d_prof || max_workgroups < 0) return VIL_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int n = std::min<int>(max_workgroups, VIL_PROF_WGS);
+    HIPCHK(hipMemcpy(times, (char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 8 * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    return VIL_OK;
+}
+int vil_debug_read_stamps(vil_ctx* c, uint64_t* out, int32_t max_launches) {
+    if (!c || !out || max_launches < 0) return VIL_ERR_INVALID_ARGUMENT;
+    const size_t n = std::min((size_t)max_launches * VIL_PROF_SLOTS, c->last_stamps.size());
+    for (size_t i = 0; i < n; ++i) out[i] = c->last_stamps[i];
+    return (int)(n / VIL_PROF_SLOTS);
+}
+int vil_debug_marg_stamps(vil_ctx* c, uint64_t* out16) {
+    if (!c || !out16 || !c->d_marg_ts) return VIL_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out16, c->d_marg_ts, 8 * 16, hipMemcpyDeviceToHost));
     return VIL_OK;
 }
 
