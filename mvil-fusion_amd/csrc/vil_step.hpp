@@ -1069,7 +1069,7 @@ struct ChainSrcStep {                      // the chain's view of the system ins
 };
 
 template <bool WLDS, class PUB, class SIDE>
-__device__ __forceinline__ bool solve_chain(const DevP& P, const SysBuf& sb, StepShared& s, double* lds, const double mu, const bool cam, double& qpart, PUB pub, SIDE side) {
+__device__ __forceinline__ bool solve_chain(const DevP& P, const SysBuf& sb, StepShared& s, double* lds, const double mu, double& qpart, PUB pub, SIDE side) {
     const int t = vil_tid();
 #ifdef VIL_STAMPS
     #define SSTAMP(k) do { if (t == 0) { long long tt_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tt_) :: "memory"); P.dbg[40 + k] = tt_; } } while (0)
@@ -1088,7 +1088,7 @@ __device__ __forceinline__ bool solve_chain(const DevP& P, const SysBuf& sb, Ste
     if (t < 384) {
         const ChainSrcStep src{sb.S, D, s.sc, s.dcs, s.gd, s.y, mu, NP};
         double qc = 0.0;
-        if (cam) chain_eliminate<true>(src, K, NP, RS, Wt, L, qc, P.dbg); else chain_eliminate<false>(src, K, NP, RS, Wt, L, qc, P.dbg);
+        chain_eliminate<true>(src, K, NP, RS, Wt, L, qc, P.dbg);
         qpart += qc;
     } else {
         // waves 6, 7 meanwhile: the pose tiles M_pp = Sc S'_pp Sc + mu dc^2 (+ rhs row) with their share of u^T S' u; four
@@ -1109,7 +1109,7 @@ __device__ __forceinline__ bool solve_chain(const DevP& P, const SysBuf& sb, Ste
                 const int i = ii[u], j = jj[u];
                 double mv = 0.0;
                 if (i < NP && j <= i) {
-                    if (cam) qpart += (i == j ? 1.0 : 2.0) * s.y[i] * v[u] * s.y[j];
+                    qpart += (i == j ? 1.0 : 2.0) * s.y[i] * v[u] * s.y[j];
                     mv = s.sc[i] * v[u] * s.sc[j];
                     if (i == j) mv += mu * s.dcs[i] * s.dcs[i];
                 } else if (i == NP && j < NP) mv = s.sc[j] * s.gd[j];
@@ -1186,7 +1186,7 @@ __device__ __forceinline__ bool solve_chain(const DevP& P, const SysBuf& sb, Ste
 //      M_pp = Sc (S'_pp - W W^T) Sc + mu d^2 (the row scaling the chain workgroup deferred is applied here), dense part, chain back
 //      substitution.  Same contract as solve_chain.
 template <bool RW /* the row-per-lane factorisation (chol_rowwave) where it applies: the one-launch iteration */, class PUB, class SIDE>
-__device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, StepShared& s, double* lds, const double mu, const bool cam, double& qpart, const int epoch /* of this launch's flags */, PUB pub, SIDE side) {
+__device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, StepShared& s, double* lds, const double mu, double& qpart, const int epoch /* of this launch's flags */, PUB pub, SIDE side) {
     const int t = vil_tid();
     SSTAMP(0);
     const int K = P.K, D = P.D, NP = P.NV, R = NP + 1, T = (R + 15) >> 4, ntile = (T * (T + 1)) >> 1;
@@ -1211,7 +1211,7 @@ __device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, 
                 const int i = ii[u], j = jj[u];
                 double mv = 0.0;
                 if (i < NP && j <= i) {
-                    if (cam) qpart += (i == j ? 1.0 : 2.0) * s.y[i] * v[u] * s.y[j];
+                    qpart += (i == j ? 1.0 : 2.0) * s.y[i] * v[u] * s.y[j];
                     mv = s.sc[i] * v[u] * s.sc[j];
                     if (i == j) mv += mu * s.dcs[i] * s.dcs[i];
                 } else if (i == NP && j < NP) mv = s.sc[j] * s.gd[j];
@@ -1242,10 +1242,9 @@ __device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, 
                 if (i <= NP && j <= i && j < NP) Tl[tl_phys(e)] -= (i < NP ? s.sc[i] : 1.0) * ww[u] * s.sc[j];
             }
         }
-        if (cam) {                                     // chain share of u^T S' u: chain x chain + 2 u_p . (S'_pb u_b)
-            if (t < NP) qpart += 2.0 * s.y[t] * (ld_ag(P.chZ + t) + ld_ag(P.chZ + R + t));
-            if (t == 0) qpart += ld_ag(P.chQ) + ld_ag(P.chQ + 1);
-        }
+        // chain share of u^T S' u: chain x chain + 2 u_p . (S'_pb u_b)
+        if (t < NP) qpart += 2.0 * s.y[t] * (ld_ag(P.chZ + t) + ld_ag(P.chZ + R + t));
+        if (t == 0) qpart += ld_ag(P.chQ) + ld_ag(P.chQ + 1);
         if (t == 0 && !ld_ag(P.chOk)) s.ok = 0;
     }
     __syncthreads();
@@ -1387,6 +1386,8 @@ __device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, 
 // FUSED: the role runs inside the one-launch iteration (k_iter, vil_iter.hpp) -- the sweep's workgroups are part of the SAME launch: the gather workgroups
 // wait for their flags (P.sflag) and read the records at agent scope, the chain workgroup waits for the IMU / prior workgroups', master and helpers read the
 // landmark arrays at agent scope, and the master counts the launch in Ctl::n_sweeps itself.  p0: the workgroup's index among the step roles.
+// DESIGN 5.2 lists the stages of step_body in order: who runs each, what it waits for, what it publishes, the barrier that closes it.
+//
 // The judge of a candidate that is a STEP (not the first linearisation, not a re-sweep): function tolerance, relative decrease, radius update (trust_region_minimizer.cc;
 // SURVEY Appendix B).  One function for the ordinary place (behind the gather) and the persistent solve's cost-first judgement (behind the sweep roles' cost partials).
 __device__ __forceinline__ void judge_step(Ctl& c, const double cand_cost, const SolveOpts& O, int& need) {
@@ -1427,6 +1428,47 @@ __device__ __forceinline__ void post_iter_header(const DevP& P, const Ctl& c, co
         __hip_atomic_store(P.ihdr + t, ((unsigned long long)(unsigned)epoch << 32) | pl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+namespace vd {
+// the dogleg diagonal of a column with scale S and Hessian diagonal h (clamped as ceres' dogleg_strategy.cc does), and the Jacobi scale of a column of the first linearisation
+__device__ __forceinline__ double dogleg_diag(const double S, const double h) { return sqrt(fmin(fmax(S * S * h, 1e-6), 1e32)); }
+__device__ __forceinline__ double jacobi_scale(const double dg) { return 1.0 / (1.0 + sqrt(dg)); }
+// entry (i, j) of the packed system from the S' entry Sij() (called only where i < D and j <= i): M = Sc S' Sc + mu dc^2, row D the scaled reduced gradient; its share of u^T S' u into q
+template <class V>
+__device__ __forceinline__ double pack_entry(const StepShared& s, const int D, const double mu, const int i, const int j, V&& Sij, double& q) {
+    double m = 0.0;
+    if (i < D && j <= i) {
+        const double v = Sij();
+        q += (i == j ? 1.0 : 2.0) * s.y[i] * v * s.y[j];
+        m = s.sc[i] * v * s.sc[j];
+        if (i == j) m += mu * s.dcs[i] * s.dcs[i];
+    } else if (i == D && j < D) m = s.sc[j] * s.gd[j];
+    return m;
+}
+// ---------------- traditional dogleg in dogleg space (scalars saved with the linearisation): step = cg gradient + cn gauss_newton, its norm, the model's decrease ----------------
+struct Dogleg { double cg, cn, dnorm, model_change; };
+__device__ __forceinline__ Dogleg dogleg_scalars(const Ctl& c) {
+    const double gn2 = c.gn2, g2 = c.g2, gg = c.gg;
+    const double radius = c.radius, alpha = c.alpha, mu_u = c.mu_used;
+    const double gn_norm = sqrt(gn2), g_norm = sqrt(g2);
+    double cg, cn, dnorm;
+    if (gn_norm <= radius) { cg = 0; cn = 1; dnorm = gn_norm; }
+    else if (g_norm * alpha >= radius) { cg = -(radius / g_norm); cn = 0; dnorm = radius; }
+    else {
+        const double b_dot_a = -alpha * gg;
+        const double a2 = (alpha * g_norm) * (alpha * g_norm);
+        const double bma2 = a2 - 2 * b_dot_a + gn2;
+        const double cc = b_dot_a - a2;
+        const double dd = sqrt(cc * cc + bma2 * (radius * radius - a2));
+        const double beta = (cc <= 0) ? (dd - cc) / bma2 : (radius * radius - a2) / (dd + cc);
+        cg = -alpha * (1 - beta); cn = beta; dnorm = radius;
+    }
+    // model decrease from the linear-algebra identities of the solved system (u = Sc gradient_/d, w = GN step):
+    //   u^T H u = g2/alpha ; H w = -g - mu (d/S)^2 w  =>  u^T H w = -g2 - mu gg ,  w^T H w = -gg - mu gn2 ;  g^T u = g2 , g^T w = gg
+    const double qd = cg * cg * (g2 / alpha) + 2.0 * cg * cn * (-g2 - mu_u * gg) + cn * cn * (-gg - mu_u * gn2);
+    const double gd = cg * g2 + cn * gg;
+    return {cg, cn, dnorm, -(0.5 * qd + gd)};
+}
+}  // namespace vd
 // duty_item >= 0 (the persistent solve, k_solve): the gather item a helper or tile workgroup of a live iteration takes once it holds Ctl and the epoch, BEFORE its own
 // waits -- it has nothing to do until the gather is complete / the chain is eliminated
 template <bool LDSM, int CHAIN, bool FUSED>
@@ -1593,7 +1635,6 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
         if (!(FUSED && P.persist)) store_ctl();      // (the persistent solve: Ctl leaves through k_solve's tail, BEHIND the hand-over line of the next iteration's sweep roles)
     };
-    const bool cam = true;             // (every rank holds the complete system: nothing is counted per rank any more)
     STAMP(0);
     // ---------------- judge the candidate that the sweep just linearised -------------------------
     if (t == 0 && !s.judged) {
@@ -1619,7 +1660,7 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
     auto lm_pass1 = [&](int l0, int l1, const double* vc, double& q, double& g2, double& gm) {
         for (int l = l0 + t; l < l1; l += NT) {
             const double ip = ldx<FUSED>(sb.invp + l), Sl = ldx<FUSED>(sb.sl + l), h = ldx<FUSED>(sb.hll + l), b = ldx<FUSED>(sb.bl + l);
-            const double d = sqrt(fmin(fmax(Sl * Sl * h, 1e-6), 1e32));
+            const double d = dogleg_diag(Sl, h);
             const double g = ip != 0.0 ? Sl * b / d : 0.0;
             P.dl[l] = d; P.gradl[l] = g;
             if (ip != 0.0) {
@@ -1703,8 +1744,8 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
             // camera vectors u = Sc gradient_/d in LDS (nothing global is written here: that is the master's job)
             for (int i = t; i < P.NV; i += NT) {
                 const double dg = merged ? ld_ag(sb.diag + i) : sb.diag[i], b = merged ? ld_ag(sb.bc + i) : sb.bc[i];
-                const double Sc = s.was_first ? (O.jacobi_scaling ? 1.0 / (1.0 + sqrt(dg)) : 1.0) : ldx<FUSED>(P.Sc + i);
-                const double d = sqrt(fmin(fmax(Sc * Sc * dg, 1e-6), 1e32));
+                const double Sc = s.was_first ? (O.jacobi_scaling ? jacobi_scale(dg) : 1.0) : ldx<FUSED>(P.Sc + i);
+                const double d = dogleg_diag(Sc, dg);
                 s.y[i] = Sc * (Sc * b / d) / d;
             }
             __syncthreads();
@@ -1728,7 +1769,7 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
                     const double Sl = ldx<FUSED>(sb.sl + l), h = ldx<FUSED>(sb.hll + l);
                     h_ = h;
                     if (!(P.lm_const && P.lm_const[l])) { const double lam = ldx<FUSED>(x + xo_lam(P) + l); lam2 = lam * lam; }
-                    d = sqrt(fmin(fmax(Sl * Sl * h, 1e-6), 1e32));
+                    d = dogleg_diag(Sl, h);
                     g = ip != 0.0 ? Sl * b / d : 0.0;
                     if (lead) { P.dl[l] = d; P.gradl[l] = g; }
                     if (ip != 0.0) { Sd = Sl / d; ipS = ip / Sl; a_ = Sd * g; }               // the divides of the second pass, done while the master solves
@@ -1848,13 +1889,13 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
         for (int i = t; i < D; i += NT) {
             const double dg = merged ? ld_ag(sb.diag + i) : sb.diag[i], b = merged ? ld_ag(sb.bc + i) : sb.bc[i];
             double Sc;
-            if (s.was_first) { Sc = O.jacobi_scaling ? 1.0 / (1.0 + sqrt(dg)) : 1.0; if (CHAIN == 3 && i >= P.NV) Sc = ld_ag(P.chSc + (i - P.NV)); stx<FUSED>(P.Sc + i, Sc); } else Sc = ldx<FUSED>(P.Sc + i);
-            double d = sqrt(fmin(fmax(Sc * Sc * dg, 1e-6), 1e32));
+            if (s.was_first) { Sc = O.jacobi_scaling ? jacobi_scale(dg) : 1.0; if (CHAIN == 3 && i >= P.NV) Sc = ld_ag(P.chSc + (i - P.NV)); stx<FUSED>(P.Sc + i, Sc); } else Sc = ldx<FUSED>(P.Sc + i);
+            double d = dogleg_diag(Sc, dg);
             if (CHAIN == 3 && i >= P.NV) d = ld_ag(P.chDc + (i - P.NV));      // the very numbers the chain workgroup scaled M_bb with
             const double g = Sc * b / d;
             s.sc[i] = Sc; s.dcs[i] = d; s.gr[i] = g; s.y[i] = Sc * g / d; s.gd[i] = merged ? ld_ag(sb.gred + i) : sb.gred[i]; s.rt[i] = Sc / d;
             P.dc[i] = d; P.gradc[i] = g;
-            if (cam) { g2 += g * g; gm = fmax(gm, fabs(b)); }
+            g2 += g * g; gm = fmax(gm, fabs(b));
         }
         __syncthreads();
         STAMP(9);
@@ -1868,8 +1909,8 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
             __syncthreads();
             auto pub = [&]() { publish_xp(1); };
             auto side = [&]() {};          // (the helpers' sums are collected after the step vectors below: their round trip outlasts the chain walks -- also with a quad of threads per landmark: fetched by the spare wave beside the walks, the walks' barrier waits for the answer instead, 46.2 -> 47.2 us, and the sums are in at the same 49.4)
-            if constexpr (CHAIN == 3) ok = solve_prechain<FUSED>(P, sb, s, Alds, mu, cam, q, epoch, pub, side);
-            else ok = solve_chain<CHAIN == 1>(P, sb, s, Alds, mu, cam, q, pub, side);      // packing, chain, Schur update, dense part, back substitution
+            if constexpr (CHAIN == 3) ok = solve_prechain<FUSED>(P, sb, s, Alds, mu, q, epoch, pub, side);
+            else ok = solve_chain<CHAIN == 1>(P, sb, s, Alds, mu, q, pub, side);      // packing, chain, Schur update, dense part, back substitution
         } else {
         // tiled storage: element e of the tile array -> (i, j); S entries were prefetched into registers at kernel start
         double* Ag = P.M;
@@ -1885,13 +1926,7 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
             if (e < NTL) {
                 const int I = half ? I1 : I0, J = half ? J1 : J0;
                 const int i = (I << 4) + (w >> 4), j = (J << 4) + (w & 15);
-                double m = 0.0;
-                if (i < D && j <= i) {
-                    const double v = pf[u];
-                    if (cam) q += (i == j ? 1.0 : 2.0) * s.y[i] * v * s.y[j];
-                    m = s.sc[i] * v * s.sc[j];
-                    if (i == j) m += mu * s.dcs[i] * s.dcs[i];
-                } else if (i == D && j < D) m = s.sc[j] * s.gd[j];
+                const double m = pack_entry(s, D, mu, i, j, [&]() { return pf[u]; }, q);
                 if constexpr (LDSM) Alds[tl_phys(e)] = m; else Ag[tl_phys(e)] = m;
             }
         });
@@ -1902,13 +1937,7 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
             const int tile = e >> 8, w = e & 255;
             const int I = s.tI[tile], J = s.tJ[tile];
             const int i = (I << 4) + (w >> 4), j = (J << 4) + (w & 15);
-            double m = 0.0;
-            if (i < D && j <= i) {
-                const double v = sb.S[(size_t)i * D + j];
-                if (cam) q += (i == j ? 1.0 : 2.0) * s.y[i] * v * s.y[j];
-                m = s.sc[i] * v * s.sc[j];
-                if (i == j) m += mu * s.dcs[i] * s.dcs[i];
-            } else if (i == D && j < D) m = s.sc[j] * s.gd[j];
+            const double m = pack_entry(s, D, mu, i, j, [&]() { return sb.S[(size_t)i * D + j]; }, q);
             if constexpr (LDSM) Alds[tl_phys(e)] = m; else Ag[tl_phys(e)] = m;
         }
         }
@@ -1971,7 +2000,7 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
             const double xi = s.y[i];
             const double gnv = -xi * s.dcs[i];
             s.gn[i] = gnv; P.gnc[i] = gnv;
-            if (cam) { gn2 += gnv * gnv; gg += gnv * s.gr[i]; }
+            gn2 += gnv * gnv; gg += gnv * s.gr[i];
             s.y[i] = s.sc[i] * xi;     // Sc x_c for the landmark back-substitution
         }
         __syncthreads();
@@ -2061,27 +2090,8 @@ __device__ __forceinline__ void step_body(const DevP& P, const SolveOpts& O, vd:
     if (t == 0 && P.abortf) abort_pre = ld_ag(P.abortf);
     // persistent solve: the helpers' la / lb (read by the visual roles of the NEXT iteration) are out -- their flags are collected by the spare wave under the dogleg's scalars
     if (FUSED && P.persist && t >= NT - 64) { if ((t & 63) < nhelp) spin_until_eq(P.hflag2 + (t & 63), epoch, P.abortf); __builtin_amdgcn_wave_barrier(); if (t == NT - 64) s.pad0_ = epoch; }
-    // ---------------- traditional dogleg in dogleg space (scalars saved with the linearisation) ----------------
-    gn2 = s.c.gn2; g2 = s.c.g2; gg = s.c.gg;
-    const double radius = s.c.radius, alpha = s.c.alpha, mu_u = s.c.mu_used;
-    const double gn_norm = sqrt(gn2), g_norm = sqrt(g2);
-    double cg, cn, dnorm;
-    if (gn_norm <= radius) { cg = 0; cn = 1; dnorm = gn_norm; }
-    else if (g_norm * alpha >= radius) { cg = -(radius / g_norm); cn = 0; dnorm = radius; }
-    else {
-        const double b_dot_a = -alpha * gg;
-        const double a2 = (alpha * g_norm) * (alpha * g_norm);
-        const double bma2 = a2 - 2 * b_dot_a + gn2;
-        const double cc = b_dot_a - a2;
-        const double dd = sqrt(cc * cc + bma2 * (radius * radius - a2));
-        const double beta = (cc <= 0) ? (dd - cc) / bma2 : (radius * radius - a2) / (dd + cc);
-        cg = -alpha * (1 - beta); cn = beta; dnorm = radius;
-    }
-    // model decrease from the linear-algebra identities of the solved system (u = Sc gradient_/d, w = GN step):
-    //   u^T H u = g2/alpha ; H w = -g - mu (d/S)^2 w  =>  u^T H w = -g2 - mu gg ,  w^T H w = -gg - mu gn2 ;  g^T u = g2 , g^T w = gg
-    const double qd = cg * cg * (g2 / alpha) + 2.0 * cg * cn * (-g2 - mu_u * gg) + cn * cn * (-gg - mu_u * gn2);
-    const double gd = cg * g2 + cn * gg;
-    const double model_change = -(0.5 * qd + gd);
+    const Dogleg dl = dogleg_scalars(s.c);
+    const double cg = dl.cg, cn = dl.cn, dnorm = dl.dnorm, model_change = dl.model_change;
     // ---------------- candidate state x_cur (+) step: camera blocks here, inverse depths in the next sweep ----------------------
     double* xcs = s.gr;                              // the candidate's camera part is formed in LDS (gr | gn: 640 doubles, dead from here on -- P.gradc / P.gnc keep them) and leaves in one pass
     static_assert(offsetof(StepShared, gn) == offsetof(StepShared, gr) + 320 * sizeof(double), "the candidate spills from gr into gn");
