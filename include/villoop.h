@@ -36,7 +36,8 @@
  * vloop_verify is performICP over a list of candidates plus the selection of findLoopClosure.  OUT OF SCOPE, left with the caller:
  *   - the skip_recent_poses, proximity_threshold and floor filters (:449-465): host bookkeeping over the pose table;
  *   - the two pcl::ApproximateVoxelGrid calls of performICP (:521-527): the caller passes the filtered clouds;
- *   - the pose graph (GTSAM) and what is done with the winner.
+ *   - what is done with the winner.  The pose graph itself is include/vilpgo.h: best.delta and best.fitness go into vpgo_add_between as they
+ *     are (:387, :498), and vpgo_relative gives the next candidate's guess (:370).
  * DEVIATION: delta is the inverse of the float-rounded result in double, (R^-1, -R^-1 t) with the 3 x 3 inverse by cofactors, so that
  * delta T is the identity to double rounding.  For an orthonormal R that is (R^T, -R^T t); the float-rounded R is orthonormal to 6e-8
  * only.  The reference goes through its own Quaternion / Pose6D types (:569-570), which renormalise the rotation instead.

@@ -10,7 +10,7 @@
  * keyframe only the scan goes up, per detection only a vsc_result comes back.
  *
  * STAYS ON THE HOST (out of scope here):
- *   - the caller's checks on the result: historyID != 0 and the floor test (:357), the GTSAM pose graph, keyframe selection;
+ *   - the caller's checks on the result: historyID != 0 and the floor test (:357), keyframe selection (the pose graph is include/vilpgo.h);
  *   - the kd-tree's rebuild schedule (TREE_MAKING_PERIOD_ = 30, Scancontext.cpp:356-368): the reference searches a tree that is up to
  *     29 keyframes stale.  This library has no tree; a caller who wants that behaviour passes the stale tree's size as n_search.
  *

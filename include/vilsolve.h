@@ -59,7 +59,8 @@ typedef enum {
     VIL_ERR_NON_FINITE = -3,       /* NaN/Inf in cost or step; state left unchanged      */
     VIL_ERR_NOT_POSITIVE_DEFINITE = -4, /* reduced system not PD after max mu             */
     VIL_ERR_COMM = -5,             /* RCCL failure                                        */
-    VIL_ERR_UNSUPPORTED = -6
+    VIL_ERR_UNSUPPORTED = -6,
+    VIL_ERR_CAPACITY = -7          /* a resident structure is full (vilpgo.h: poses, factors, separators)  */
 } vil_status;
 
 typedef enum {

@@ -1,5 +1,5 @@
 // vil_host.hpp -- the host scaffold shared by the row libraries (vilmap.hip, vilvgicp.hip, vilpreint.hip, vilscan.hip, vildepth.hip,
-// vilsc.hip, villoop.hip): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers and the kernel-event profiler.
+// vilsc.hip, villoop.hip, vilpgo.hip): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers and the kernel-event profilers.
 // Header-only, internal linkage: libvilsolve.so exports nothing from here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/vilsolve.h"
 
@@ -49,6 +50,38 @@ struct Profiler {
         for (int k = 0; k < NK; ++k) { launches[k] = n[k]; total_ms[k] = ms[k]; n[k] = 0; ms[k] = 0.0; }
     }
     void destroy() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+};
+
+// The same for a call whose number of launches is not fixed (vilpgo.hip: an enqueued sequence per iteration): mark() records an event before a
+// group of launches of one kernel and grows the pool on demand, collect() -- after the call's synchronisation -- gives the time between
+// two marks to the first one's kernel.  kernel < 0 closes the last group.
+template <int NK>
+struct EventLog {
+    struct Mark { int kernel, launches; };
+    bool on = false;
+    std::vector<hipEvent_t> ev;
+    std::vector<Mark> marks;
+    long long n[NK] = {};
+    double ms[NK] = {};
+
+    hipError_t mark(int kernel, int launches, hipStream_t stream) {
+        if (!on) return hipSuccess;
+        if (marks.size() == ev.size()) { hipEvent_t e; const hipError_t err = hipEventCreate(&e); if (err != hipSuccess) return err; ev.push_back(e); }
+        const hipError_t err = hipEventRecord(ev[marks.size()], stream);
+        if (err == hipSuccess) marks.push_back({kernel, launches});
+        return err;
+    }
+    void collect() {
+        for (size_t i = 0; i + 1 < marks.size(); ++i) {
+            float t = 0.f;
+            if (marks[i].kernel >= 0 && hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { ms[marks[i].kernel] += t; n[marks[i].kernel] += marks[i].launches; }
+        }
+        marks.clear();
+    }
+    void read(int64_t* launches, double* total_ms) {
+        for (int k = 0; k < NK; ++k) { launches[k] = n[k]; total_ms[k] = ms[k]; n[k] = 0; ms[k] = 0.0; }
+    }
+    void destroy() { for (hipEvent_t e : ev) hipEventDestroy(e); }
 };
 
 inline bool has_device(int dev) {                          // no CPU fallback

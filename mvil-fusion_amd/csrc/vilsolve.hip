@@ -466,6 +466,7 @@ const char* vil_strerror(int st) {
         case VIL_ERR_NOT_POSITIVE_DEFINITE: return "reduced system not positive definite";
         case VIL_ERR_COMM: return "RCCL error";
         case VIL_ERR_UNSUPPORTED: return "unsupported configuration";
+        case VIL_ERR_CAPACITY: return "capacity exceeded";
     }
     return "unknown";
 }
