@@ -28,6 +28,25 @@ def test_preintegration_argument_checks():
     p.close()
 
 
+def test_imu_covariance_not_positive_definite_is_a_status(hip):
+    """k_setup meets an IMU covariance with a negative diagonal entry through the plain upload: vil_upload returns
+    VIL_ERR_NOT_POSITIVE_DEFINITE, the state handed in is not touched, and the context then solves the unmodified window as before."""
+    from mvil_fusion_amd import synth
+    state = lambda w: np.concatenate([w.pose.ravel(), w.speedbias.ravel(), w.ex_pose, w.td, w.inv_depth])
+    good = synth.make_config(1)
+    s0 = hip.solve(good)
+    bad = synth.make_config(1)
+    bad.imu_const[1, 62 + 16 * 7] = -abs(bad.imu_const[1, 62 + 16 * 7])      # P[7, 7] < 0
+    before = state(bad)
+    with pytest.raises(lib.VilError) as e:
+        hip.upload(bad)
+    assert e.value.status == -4                                             # VIL_ERR_NOT_POSITIVE_DEFINITE
+    assert np.array_equal(state(bad), before)
+    again = synth.make_config(1)
+    s1 = hip.solve(again)
+    assert (s1.iterations, s1.termination, s1.final_cost) == (s0.iterations, s0.termination, s0.final_cost) and np.array_equal(state(again), state(good))
+
+
 def test_mapreg_argument_checks(hip):
     so = lib.load_vilsolve()
     m = mapreg.MapReg(so, "vmap_")
