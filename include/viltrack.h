@@ -13,8 +13,8 @@
  *
  * STAYS ON THE HOST (out of scope here):
  *   - CLAHE (equalize: 1, :87-93): the caller passes the equalised image.
- *   - rejectWithF (:169-197): RANSAC on OpenCV's own random number generator.
- *   - undistortedPoints (:240-310) and the camera models.
+ *   - rejectWithF (:169-202) and undistortedPoints (:258-306) with the PINHOLE camera model: not here, but on the device all the same,
+ *     in the row of their own behind vilepi.h (vepi_reject, vepi_undistort).
  *   - ids, track_cnt, reduceVector and addPoints: the caller compacts its vectors on `status` and `kept`.
  *   - the sort by track_cnt in setMask (:50-53): an unstable std::sort; tracks_xy arrives in the caller's priority order.
  *   - the PUB_THIS_FRAME schedule: vtrack_detect is called when the reference would call setMask.
