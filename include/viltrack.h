@@ -12,7 +12,8 @@
  * order: the device equals tests/track_ref.py bit for bit with no summation order to agree on.
  *
  * STAYS ON THE HOST (out of scope here):
- *   - CLAHE (equalize: 1, :87-93): the caller passes the equalised image.
+ *   - CLAHE (equalize: 1, :87-93): not here, but on the device all the same, in the row behind vilclahe.h: vclahe_push equalises the raw
+ *     image straight into this tracker's next image and builds its pyramid; vtrack_push_image takes an image as it is.
  *   - rejectWithF (:169-202) and undistortedPoints (:258-306) with the PINHOLE camera model: not here, but on the device all the same,
  *     in the row of their own behind vilepi.h (vepi_reject, vepi_undistort).
  *   - ids, track_cnt, reduceVector and addPoints: the caller compacts its vectors on `status` and `kept`.

@@ -2,7 +2,8 @@
 // :81-167; the steps are numbered as in the header).
 //
 // Both images' pyramids are resident; vtrack_push_image flips which slot is cur and which is forw.  Every entry point is one submission on
-// the context's stream with one read-back.
+// the context's stream with one read-back.  vtrack_push_image is two stages, the upload into level 0 of the next slot and everything after
+// it (viltrack_stage.hpp): vilclahe.hip produces level 0 on the device and shares the second.
 //   k_track_pyr    a thread per pixel of level l+1: step 1, 25 bytes through r101.  One launch per level.
 //   k_track_lk     a WAVE (= workgroup of 64) per point, the whole level loop in one launch: steps 3-6.  The 22 x 22 samples a window needs
 //                  (image and, for the template, the Scharr derivatives computed on the fly from the image, step 2) are staged in LDS; a
@@ -35,6 +36,7 @@
 
 #include "../../include/viltrack.h"
 #include "vil_host.hpp"
+#include "viltrack_stage.hpp"
 
 #define VT_PATCH 22                       // VTRACK_WIN + 1 samples per side
 #define VT_PATCH2 (VT_PATCH * VT_PATCH)
@@ -464,6 +466,31 @@ struct vtrack_ctx : vilhost::Device {        // d_mem: pyramid slot 0 | slot 1 |
     vilhost::Profiler<VTRACK_NUM_KERNELS, 8> prof;
 };
 
+// ---- the stages of vtrack_push_image (viltrack_stage.hpp) ------------------------------------------------------------------------
+// the slot the next image goes to: never the slot of the image that becomes cur
+static int next_slot(const vtrack_ctx* c) { return c->n_images ? 1 - c->forw : 0; }
+
+viltrack_stage::Target viltrack_stage::target(const vtrack_ctx* c) {
+    return {(uint8_t*)(c->d_mem + c->o_slot[next_slot(c)] + c->loff[0]), c->stream, c->device, c->cfg.width, c->cfg.height};
+}
+
+int viltrack_stage::finish_push(vtrack_ctx* c) {
+    const int L = c->cfg.max_level, slot = next_slot(c);
+    uint8_t* base = (uint8_t*)(c->d_mem + c->o_slot[slot]);
+    for (int l = 0; l < L; ++l) {
+        VILCHK(c->prof.mark(l, c->stream));
+        const int n2 = c->lw[l + 1] * c->lh[l + 1];
+        hipLaunchKernelGGL(k_track_pyr, dim3((n2 + 255) / 256), dim3(256), 0, c->stream, base + c->loff[l], c->lw[l], c->lh[l], base + c->loff[l + 1], c->lw[l + 1], c->lh[l + 1]);
+    }
+    VILCHK(c->prof.mark(L, c->stream));
+    VILCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipGetLastError());
+    for (int l = 0; l < L; ++l) c->prof.span(0, l, l + 1);
+    c->cur = c->n_images ? c->forw : slot; c->forw = slot;
+    if (c->n_images < 2) c->n_images++;
+    return VIL_OK;
+}
+
 extern "C" {
 
 int vtrack_create(int32_t device, const vtrack_cfg* cfg, vtrack_ctx** out) {
@@ -526,23 +553,10 @@ int vtrack_profile_read(vtrack_ctx* c, int64_t* launches8, double* total_ms8) {
 int vtrack_push_image(vtrack_ctx* c, const uint8_t* gray, int32_t row_stride) {
     if (!c || !gray || row_stride < c->cfg.width) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    const int W = c->cfg.width, H = c->cfg.height, L = c->cfg.max_level;
-    const int slot = c->n_images ? 1 - c->forw : 0;         // never the slot of the image that becomes cur
+    const int W = c->cfg.width, H = c->cfg.height;
     for (int y = 0; y < H; ++y) memcpy(c->h_img + (size_t)y * W, gray + (size_t)y * row_stride, W);
-    uint8_t* base = (uint8_t*)(c->d_mem + c->o_slot[slot]);
-    VILCHK(hipMemcpyAsync(base, c->h_img, (size_t)W * H, hipMemcpyHostToDevice, c->stream));
-    for (int l = 0; l < L; ++l) {
-        VILCHK(c->prof.mark(l, c->stream));
-        const int n2 = c->lw[l + 1] * c->lh[l + 1];
-        hipLaunchKernelGGL(k_track_pyr, dim3((n2 + 255) / 256), dim3(256), 0, c->stream, base + c->loff[l], c->lw[l], c->lh[l], base + c->loff[l + 1], c->lw[l + 1], c->lh[l + 1]);
-    }
-    VILCHK(c->prof.mark(L, c->stream));
-    VILCHK(hipStreamSynchronize(c->stream));
-    VILCHK(hipGetLastError());
-    for (int l = 0; l < L; ++l) c->prof.span(0, l, l + 1);
-    c->cur = c->n_images ? c->forw : slot; c->forw = slot;
-    if (c->n_images < 2) c->n_images++;
-    return VIL_OK;
+    VILCHK(hipMemcpyAsync(viltrack_stage::target(c).level0, c->h_img, (size_t)W * H, hipMemcpyHostToDevice, c->stream));
+    return viltrack_stage::finish_push(c);
 }
 
 int vtrack_track(vtrack_ctx* c, int32_t n, const float* cur_xy, float* forw_xy, uint8_t* status, vtrack_summary* out) {
