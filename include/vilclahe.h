@@ -10,7 +10,8 @@
  * BITS.  Histogram, clip, redistribution and prefix sum are integer work, exact in any order; the only floating point is a four-term f32
  * blend per pixel in a fixed order, so the device equals tests/clahe_ref.py bit for bit.
  *
- * OUT OF SCOPE: 16-bit images.
+ * OUT OF SCOPE: 16-bit images.  The rest of readImage after the equalisation is not here but in vilfeat.h: vfeat_read_image runs these
+ * kernels (cfg.equalize) in front of tracking, rejection, detection and the bookkeeping, in one call.
  *
  * ARITHMETIC CONTRACT.  f32 is unfused IEEE float32 in the order written; everything else is integer.  r101 is the one of viltrack.h.
  * W, H the image, tiles_x, tiles_y, clip_limit the configuration.

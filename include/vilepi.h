@@ -17,7 +17,8 @@
  *   - the generator is the counter-based one of step 3, not cv::RNG.
  *   - when no hypothesis reaches 8 inliers the reference is left with an empty status and reads past it; here status is all 1,
  *     best_hypothesis = -1, found = 0 and the call returns VIL_OK (step 7).
- * STAYS ON THE HOST: reduceVector on `status`, the ids / track_cnt bookkeeping, the other camodocal models (VIL_ERR_UNSUPPORTED).
+ * STAYS ON THE HOST: reduceVector on `status`, the ids / track_cnt bookkeeping (both on the device in vfeat_read_image, vilfeat.h, which
+ * runs the kernels of this row on resident points), the other camodocal models (VIL_ERR_UNSUPPORTED).
  *
  * ARITHMETIC CONTRACT.  f64 is unfused IEEE double in the order written (a op b op c is (a op b) op c); f32(x) rounds to nearest even.
  *   1 lift        inv_K11 = 1/fx, inv_K13 = -cx/fx, inv_K22 = 1/fy, inv_K23 = -cy/fy (computed once, on the host).  For a pixel (u, v) given

@@ -16,8 +16,10 @@
  *     image straight into this tracker's next image and builds its pyramid; vtrack_push_image takes an image as it is.
  *   - rejectWithF (:169-202) and undistortedPoints (:258-306) with the PINHOLE camera model: not here, but on the device all the same,
  *     in the row of their own behind vilepi.h (vepi_reject, vepi_undistort).
- *   - ids, track_cnt, reduceVector and addPoints: the caller compacts its vectors on `status` and `kept`.
- *   - the sort by track_cnt in setMask (:50-53): an unstable std::sort; tracks_xy arrives in the caller's priority order.
+ *   - ids, track_cnt, reduceVector and addPoints: the caller compacts its vectors on `status` and `kept` -- or leaves all of it on the
+ *     device: vfeat_read_image (vilfeat.h) is readImage as one call over the kernels of this row, with the points resident.
+ *   - the sort by track_cnt in setMask (:50-53): an unstable std::sort; tracks_xy arrives in the caller's priority order (vilfeat.h
+ *     fixes it as the stable order).
  *   - the PUB_THIS_FRAME schedule: vtrack_detect is called when the reference would call setMask.
  *   - the fisheye mask (FISHEYE, :38-39): the mask of step 7 starts as all 255.
  *

@@ -28,6 +28,7 @@
 
 #include "../../include/vilclahe.h"
 #include "vil_host.hpp"
+#include "vilclahe_stage.hpp"
 #include "viltrack_stage.hpp"
 
 #define VC_SHARE 1024                     // pixels of a tile that a workgroup of k_clahe_hist takes, at least
@@ -169,12 +170,16 @@ struct vclahe_ctx : vilhost::Device {        // d_mem: histograms | LUTs | the r
     vilhost::Profiler<VCLAHE_NUM_KERNELS, 4> prof;
 };
 
-// upload and the three launches on `stream`; the equalised image goes to dst and, when not NULL, to dst2 (W x H bytes, rows W apart)
-static int enqueue(vclahe_ctx* c, hipStream_t stream, const uint8_t* gray, const int row_stride, uint8_t* dst, uint8_t* dst2) {
+// ---- the stages (vilclahe_stage.hpp) ---------------------------------------------------------------------------------------------
+vilclahe_stage::Staged vilclahe_stage::stage_image(vclahe_ctx* c, const uint8_t* gray, const int row_stride) {
+    const int W = c->cfg.width, H = c->cfg.height;
+    for (int y = 0; y < H; ++y) memcpy(c->h_img + (size_t)y * W, gray + (size_t)y * row_stride, W);
+    return {(const uint8_t*)c->h_img, (uint8_t*)(c->d_mem + c->o_src)};
+}
+
+int vilclahe_stage::enqueue_kernels(vclahe_ctx* c, hipStream_t stream, uint8_t* dst, uint8_t* dst2) {
     const int W = c->cfg.width, H = c->cfg.height, tiles = c->cfg.tiles_x * c->cfg.tiles_y, groups = (W + 3) / 4;
     char* d = c->d_mem;
-    for (int y = 0; y < H; ++y) memcpy(c->h_img + (size_t)y * W, gray + (size_t)y * row_stride, W);
-    VILCHK(hipMemcpyAsync(d + c->o_src, c->h_img, (size_t)W * H, hipMemcpyHostToDevice, stream));
     VILCHK(hipMemsetAsync(d + c->o_hist, 0, (size_t)tiles * 1024, stream));
     const uint8_t* src = (const uint8_t*)(d + c->o_src);
     VILCHK(c->prof.mark(0, stream));
@@ -186,6 +191,13 @@ static int enqueue(vclahe_ctx* c, hipStream_t stream, const uint8_t* gray, const
                        c->cfg.tiles_x, c->cfg.tiles_y, c->inv_tw, c->inv_th, dst, dst2);
     VILCHK(c->prof.mark(3, stream));
     return VIL_OK;
+}
+
+// upload and the three launches on `stream`; the equalised image goes to dst and, when not NULL, to dst2 (W x H bytes, rows W apart)
+static int enqueue(vclahe_ctx* c, hipStream_t stream, const uint8_t* gray, const int row_stride, uint8_t* dst, uint8_t* dst2) {
+    const vilclahe_stage::Staged s = vilclahe_stage::stage_image(c, gray, row_stride);
+    VILCHK(hipMemcpyAsync(s.dev, s.host, (size_t)c->cfg.width * c->cfg.height, hipMemcpyHostToDevice, stream));
+    return vilclahe_stage::enqueue_kernels(c, stream, dst, dst2);
 }
 
 static void account(vclahe_ctx* c, uint8_t* out, const int out_stride) {

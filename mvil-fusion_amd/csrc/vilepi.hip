@@ -26,6 +26,7 @@
 
 #include "../../include/vilepi.h"
 #include "vil_host.hpp"
+#include "vilepi_stage.hpp"
 
 #define VE_MAX_DRAWS 65536                // step 3 gives up (no model) after this many draws: n = 8 needs 22 on average, the chance of 65536 is (7/8)^65000
 
@@ -52,15 +53,18 @@ __device__ __forceinline__ void lift(const Cam& c, const float u, const float v,
     }
 }
 
-// step 2: in holds the n points of cur, then the n points of forw
-__global__ __launch_bounds__(256) void k_epi_lift(const Cam cam, int n, const float2* __restrict__ in, float2* __restrict__ p1, float2* __restrict__ p2) {
+// step 2: threads 0 .. n_max - 1 take the points of cur, the next n_max those of forw.  n_dev: NULL, or where the count is read from (<= n_max)
+__global__ __launch_bounds__(256) void k_epi_lift(const Cam cam, int n_max, const int* __restrict__ n_dev, const float2* __restrict__ cur, const float2* __restrict__ forw,
+                                                  float2* __restrict__ p1, float2* __restrict__ p2) {
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 2 * n) return;
-    const float2 p = in[t];
+    if (t >= 2 * n_max) return;
+    const int second = t >= n_max ? 1 : 0, i = t - second * n_max;
+    if (i >= (n_dev ? min(n_max, *n_dev) : n_max)) return;
+    const float2 p = second ? forw[i] : cur[i];
     double x, y;
     lift(cam, p.x, p.y, x, y);
     const float2 o = make_float2((float)(cam.focal * x + cam.half_w), (float)(cam.focal * y + cam.half_h));
-    if (t < n) p1[t] = o; else p2[t - n] = o;                                                       // t - n < n
+    if (second) p2[i] = o; else p1[i] = o;
 }
 
 // ---- steps 3-5 -------------------------------------------------------------------------------------------------------------------
@@ -114,11 +118,16 @@ __device__ __forceinline__ int smallest(const double* A) {
     return best;
 }
 
-__global__ __launch_bounds__(64) void k_epi_hyp(int n, int h0, unsigned long long seed, double thr2, const float2* __restrict__ p1, const float2* __restrict__ p2,
-                                                int* __restrict__ samples, int* __restrict__ counts, double* __restrict__ margins, double* __restrict__ Fout,
-                                                unsigned long long* __restrict__ bits, int stride) {
+// n_dev: NULL, or where the count is read from; below the minimal sample there is nothing to do (the host does not launch for such an n)
+__global__ __launch_bounds__(64) void k_epi_hyp(int n, const int* __restrict__ n_dev, int h0, unsigned long long seed, double thr2, const float2* __restrict__ p1,
+                                                const float2* __restrict__ p2, int* __restrict__ samples, int* __restrict__ counts, double* __restrict__ margins,
+                                                double* __restrict__ Fout, unsigned long long* __restrict__ bits, int stride) {
     __shared__ double s_A[81], s_V[81], s_R[72], s_M[9], s_W[9], s_Fn[9], s_nrm[6];
     __shared__ int s_idx[VEPI_SAMPLE], s_ok[3];
+    if (n_dev) {
+        n = min(n, *n_dev);
+        if (n < VEPI_SAMPLE) return;                                                                // the whole workgroup, before any barrier
+    }
     const int lane = threadIdx.x, h = h0 + blockIdx.x;                                              // h < max_iters: the host clips the grid
     if (lane == 0) {                                                                                // step 3
         const unsigned long long base = seed ^ ((unsigned long long)h * 0xD1342543DE82EF95ull);
@@ -232,13 +241,14 @@ __global__ __launch_bounds__(64) void k_epi_hyp(int n, int h0, unsigned long lon
 }
 
 // ---- step 8 ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_epi_undist(const Cam cam, int n, const float2* __restrict__ xy, const int* __restrict__ ids, double dt, int n_prev,
-                                                    const int* __restrict__ prev_ids, const float2* __restrict__ prev_un, int* __restrict__ new_ids,
+__global__ __launch_bounds__(256) void k_epi_undist(const Cam cam, int n, const int* __restrict__ n_dev, const float2* __restrict__ xy, const int* __restrict__ ids, double dt,
+                                                    int n_prev, const int* __restrict__ prev_ids, const float2* __restrict__ prev_un, int* __restrict__ new_ids,
                                                     float2* __restrict__ new_un, float2* __restrict__ un_out, float2* __restrict__ vel_out) {
     __shared__ int s_ids[VEPI_MAX_POINTS_LIMIT];
     for (int j = threadIdx.x; j < n_prev; j += 256) s_ids[j] = prev_ids[j];                         // n_prev <= max_points <= VEPI_MAX_POINTS_LIMIT
     __syncthreads();
     const int t = blockIdx.x * 256 + threadIdx.x;
+    if (n_dev) n = min(n, *n_dev);
     if (t >= n) return;
     const float2 p = xy[t];
     double x, y;
@@ -279,6 +289,30 @@ struct vepi_ctx : vilhost::Device {          // d_mem: cur, forw | p1 | p2 | sam
     int dbg_n = 0, dbg_eval = 0, dbg_best = -1;
     vilhost::EventLog<VEPI_NUM_KERNELS> prof;
 };
+
+// ---- the stages (vilepi_stage.hpp): the launches, on the caller's pointers and stream ---------------------------------------------
+vilepi_stage::Buffers vilepi_stage::buffers(const vepi_ctx* c) {
+    char* d = c->d_mem;
+    return {(float2*)(d + c->o_p1), (float2*)(d + c->o_p2), (int*)(d + c->o_samples), (int*)(d + c->o_counts), (double*)(d + c->o_margins), (double*)(d + c->o_F),
+            (unsigned long long*)(d + c->o_bits), c->words};
+}
+
+void vilepi_stage::lift(const vepi_ctx* c, hipStream_t stream, const int n_max, const int* d_n, const float2* cur, const float2* forw, float2* p1, float2* p2) {
+    hipLaunchKernelGGL(k_epi_lift, dim3((2 * n_max + 255) / 256), dim3(256), 0, stream, c->cam, n_max, d_n, cur, forw, p1, p2);
+}
+
+void vilepi_stage::hypotheses(const vepi_ctx* c, hipStream_t stream, const int n_max, const int* d_n, const int h0, const int B, const uint64_t seed, const double thr2,
+                              const Buffers& b, int* counts, unsigned long long* bits) {
+    hipLaunchKernelGGL(k_epi_hyp, dim3(B), dim3(64), 0, stream, n_max, d_n, h0, (unsigned long long)seed, thr2, (const float2*)b.p1, (const float2*)b.p2, b.samples, counts,
+                       b.margins, b.F, bits, b.words);
+}
+
+void vilepi_stage::undistort(const vepi_ctx* c, hipStream_t stream, const int n_max, const int* d_n, const float2* xy, const int* ids, const double dt, const int n_prev,
+                             const int* prev_ids, const float2* prev_un, int* new_ids, float2* new_un, float2* un_out, float2* vel_out) {
+    hipLaunchKernelGGL(k_epi_undist, dim3((n_max + 255) / 256), dim3(256), 0, stream, c->cam, n_max, d_n, xy, ids, dt, n_prev, prev_ids, prev_un, new_ids, new_un, un_out, vel_out);
+}
+
+int vilepi_stage::update_iters(const double confidence, const double outlier_ratio, const int max_iters) { return ::update_iters(confidence, outlier_ratio, max_iters); }
 
 extern "C" {
 
@@ -361,15 +395,15 @@ int vepi_reject(vepi_ctx* c, int32_t n, const float* cur_xy, const float* forw_x
     memcpy(c->h_in, cur_xy, 8 * (size_t)n); memcpy(c->h_in + 8 * (size_t)n, forw_xy, 8 * (size_t)n);
     VILCHK(hipMemcpyAsync(d + c->o_in, c->h_in, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     VILCHK(c->prof.mark(0, 1, c->stream));
-    hipLaunchKernelGGL(k_epi_lift, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, c->cam, n, (const float2*)(d + c->o_in), (float2*)(d + c->o_p1), (float2*)(d + c->o_p2));
+    const vilepi_stage::Buffers buf = vilepi_stage::buffers(c);
+    vilepi_stage::lift(c, c->stream, n, nullptr, (const float2*)(d + c->o_in), (const float2*)(d + c->o_in) + n, buf.p1, buf.p2);
     c->dbg_n = n; c->dbg_eval = 0; c->dbg_best = -1;
     int niters = max_iters, h = 0, best = 0, best_h = -1, h0 = 0;                                   // step 6
     const int* cnt = pinned ? (const int*)c->h_res : (const int*)c->h_out;                          // counts of hypotheses h0 ..: at cnt[pinned ? h : h - h0]
     while (h < niters) {
         const int B = std::min(c->cfg.batch, niters - h0);                                          // h == h0 here; h0 + B <= niters <= max_iters
         VILCHK(c->prof.mark(1, 1, c->stream));
-        hipLaunchKernelGGL(k_epi_hyp, dim3(B), dim3(64), 0, c->stream, n, h0, (unsigned long long)seed, thr * thr, (const float2*)(d + c->o_p1), (const float2*)(d + c->o_p2),
-                           (int*)(d + c->o_samples), c->k_counts, (double*)(d + c->o_margins), (double*)(d + c->o_F), c->k_bits, c->words);
+        vilepi_stage::hypotheses(c, c->stream, n, nullptr, h0, B, seed, thr * thr, buf, c->k_counts, c->k_bits);
         VILCHK(c->prof.mark(-1, 0, c->stream));
         if (!pinned) VILCHK(hipMemcpyAsync(c->h_out, d + c->o_counts + 4 * (size_t)h0, 4 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
         VILCHK(hipStreamSynchronize(c->stream));
@@ -413,9 +447,9 @@ int vepi_undistort(vepi_ctx* c, int32_t n, const float* xy, const int32_t* ids, 
         memcpy(c->h_in, xy, 8 * (size_t)n); memcpy(c->h_in + 8 * (size_t)n, ids, 4 * (size_t)n);
         VILCHK(hipMemcpyAsync(d + c->o_uin, c->h_in, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
         VILCHK(c->prof.mark(2, 1, c->stream));
-        hipLaunchKernelGGL(k_epi_undist, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->cam, n, (const float2*)(d + c->o_uin), (const int*)(d + c->o_uin + 8 * (size_t)n), dt,
-                           c->n_tab, (const int*)(d + c->o_tab[c->tab]), (const float2*)(d + c->o_tab[c->tab] + 4 * P), (int*)(d + c->o_tab[nt]), (float2*)(d + c->o_tab[nt] + 4 * P),
-                           (float2*)(d + c->o_uout), (float2*)(d + c->o_uout + 8 * (size_t)n));
+        vilepi_stage::undistort(c, c->stream, n, nullptr, (const float2*)(d + c->o_uin), (const int*)(d + c->o_uin + 8 * (size_t)n), dt, c->n_tab,
+                                (const int*)(d + c->o_tab[c->tab]), (const float2*)(d + c->o_tab[c->tab] + 4 * P), (int*)(d + c->o_tab[nt]), (float2*)(d + c->o_tab[nt] + 4 * P),
+                                (float2*)(d + c->o_uout), (float2*)(d + c->o_uout + 8 * (size_t)n));
         VILCHK(c->prof.mark(-1, 0, c->stream));
         VILCHK(hipMemcpyAsync(c->h_out, d + c->o_uout, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
         VILCHK(hipStreamSynchronize(c->stream));

@@ -45,10 +45,9 @@
 #define VT_ONE_WG 1024
 #define VT_ROUNDS 4                       // rounds of step 10's fixpoint that run device-wide before the single workgroup finishes it
 
-namespace {
+using namespace viltrack_stage;                           // the counters of one detection, H_*
 
-// counters of one vtrack_detect (ints), read back in front of kept and new_xy
-enum { H_NKEPT = 0, H_MAXBITS, H_NCAND, H_NPICK, H_NNEW, H_ROUNDS, H_FAIL, H_INTS = 16 };
+namespace {
 
 __device__ __forceinline__ int r101(int i, const int n) {
     if ((unsigned)i < (unsigned)n) return i;
@@ -117,11 +116,13 @@ __device__ __forceinline__ int lk_interp(const short* s, const int q, const Weig
     return (w.w00 * (int)s[q] + w.w01 * (int)s[q + 1] + w.w10 * (int)s[q + VT_PATCH] + w.w11 * (int)s[q + VT_PATCH + 1] + rnd) >> sh;
 }
 
-__global__ __launch_bounds__(64) void k_track_lk(int n, int L, const int4* __restrict__ lvl, const uint8_t* __restrict__ cur, const uint8_t* __restrict__ forw,
+// n_dev: NULL, or where the count is read from (<= n, the size of the grid)
+__global__ __launch_bounds__(64) void k_track_lk(int n, const int* __restrict__ n_dev, int L, const int4* __restrict__ lvl, const uint8_t* __restrict__ cur, const uint8_t* __restrict__ forw,
                                                  const float* __restrict__ pts, float* __restrict__ out, uint8_t* __restrict__ status_out, uint8_t* __restrict__ codes,
                                                  uint8_t* __restrict__ iters) {
     __shared__ short s_i[VT_PATCH2], s_ix[VT_PATCH2], s_iy[VT_PATCH2];
     const int i = blockIdx.x, lane = threadIdx.x;
+    if (n_dev) n = min(n, *n_dev);
     if (i >= n) return;
     const float ptx = pts[2 * i], pty = pts[2 * i + 1];
     int q[VT_PER_LANE];                                     // this lane's window positions in the staged patch; -1: none
@@ -216,12 +217,13 @@ __global__ __launch_bounds__(64) void k_track_lk(int n, int L, const int4* __res
 }
 
 // ---- step 7 ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VT_ONE_WG) void k_track_mask(int n, const float* __restrict__ tracks, int md, int W, int H, uint8_t* __restrict__ kept,
+__global__ __launch_bounds__(VT_ONE_WG) void k_track_mask(int n, const int* __restrict__ n_dev, const float* __restrict__ tracks, int md, int W, int H, uint8_t* __restrict__ kept,
                                                           int* __restrict__ hdr) {
     __shared__ int s_px[VTRACK_MAX_POINTS_LIMIT], s_py[VTRACK_MAX_POINTS_LIMIT];
     __shared__ volatile uint8_t s_st[VTRACK_MAX_POINTS_LIMIT];                                       // 0 undecided, 1 kept, 2 dropped
     __shared__ int s_kept;
     const int t = threadIdx.x;
+    if (n_dev) n = min(n, *n_dev);                                                                   // the same in every thread
     if (t == 0) s_kept = 0;
     for (int i = t; i < n; i += VT_ONE_WG) {                                                         // n <= VTRACK_MAX_POINTS_LIMIT (checked by the host)
         const float rx = rintf(tracks[2 * i]), ry = rintf(tracks[2 * i + 1]);
@@ -262,8 +264,10 @@ __global__ __launch_bounds__(VT_ONE_WG) void k_track_mask(int n, const float* __
 }
 
 // the mask: a workgroup per track paints the disc of a kept one (every writer writes 0)
-__global__ __launch_bounds__(256) void k_track_paint(const float* __restrict__ tracks, const uint8_t* __restrict__ kept, int md, int W, int H, uint8_t* __restrict__ mask) {
+__global__ __launch_bounds__(256) void k_track_paint(const int* __restrict__ n_dev, const float* __restrict__ tracks, const uint8_t* __restrict__ kept, int md, int W, int H,
+                                                   uint8_t* __restrict__ mask) {
     const int i = blockIdx.x;
+    if (n_dev && i >= *n_dev) return;
     if (!kept[i]) return;                                                                           // kept: inside the image, so the casts are defined
     const int cx = (int)rintf(tracks[2 * i]), cy = (int)rintf(tracks[2 * i + 1]);
     const int side = 2 * md + 1, area = side * side, md2 = md * md;                                // md <= VTRACK_MAX_MIN_DIST: area < 2^23
@@ -474,7 +478,13 @@ viltrack_stage::Target viltrack_stage::target(const vtrack_ctx* c) {
     return {(uint8_t*)(c->d_mem + c->o_slot[next_slot(c)] + c->loff[0]), c->stream, c->device, c->cfg.width, c->cfg.height};
 }
 
-int viltrack_stage::finish_push(vtrack_ctx* c) {
+const uint8_t* viltrack_stage::stage_image(vtrack_ctx* c, const uint8_t* gray, const int row_stride) {
+    const int W = c->cfg.width, H = c->cfg.height;
+    for (int y = 0; y < H; ++y) memcpy(c->h_img + (size_t)y * W, gray + (size_t)y * row_stride, W);
+    return (const uint8_t*)c->h_img;
+}
+
+int viltrack_stage::enqueue_push(vtrack_ctx* c) {
     const int L = c->cfg.max_level, slot = next_slot(c);
     uint8_t* base = (uint8_t*)(c->d_mem + c->o_slot[slot]);
     for (int l = 0; l < L; ++l) {
@@ -483,11 +493,63 @@ int viltrack_stage::finish_push(vtrack_ctx* c) {
         hipLaunchKernelGGL(k_track_pyr, dim3((n2 + 255) / 256), dim3(256), 0, c->stream, base + c->loff[l], c->lw[l], c->lh[l], base + c->loff[l + 1], c->lw[l + 1], c->lh[l + 1]);
     }
     VILCHK(c->prof.mark(L, c->stream));
-    VILCHK(hipStreamSynchronize(c->stream));
-    VILCHK(hipGetLastError());
-    for (int l = 0; l < L; ++l) c->prof.span(0, l, l + 1);
+    return VIL_OK;
+}
+
+void viltrack_stage::commit_push(vtrack_ctx* c) {
+    const int slot = next_slot(c);
     c->cur = c->n_images ? c->forw : slot; c->forw = slot;
     if (c->n_images < 2) c->n_images++;
+}
+
+int viltrack_stage::finish_push(vtrack_ctx* c) {
+    const int st = enqueue_push(c);
+    if (st != VIL_OK) return st;
+    VILCHK(hipStreamSynchronize(c->stream));
+    VILCHK(hipGetLastError());
+    for (int l = 0; l < c->cfg.max_level; ++l) c->prof.span(0, l, l + 1);
+    commit_push(c);
+    return VIL_OK;
+}
+
+void viltrack_stage::forget(vtrack_ctx* c) { c->n_images = 0; c->forw = c->cur = 0; }
+
+int viltrack_stage::enqueue_lk(vtrack_ctx* c, const int n_max, const int* d_n, const float* d_pts, float* d_forw, uint8_t* d_status) {
+    char* d = c->d_mem;
+    VILCHK(c->prof.mark(0, c->stream));
+    hipLaunchKernelGGL(k_track_lk, dim3(n_max), dim3(64), 0, c->stream, n_max, d_n, c->cfg.max_level, (const int4*)(d + c->o_lvl), (const uint8_t*)(d + c->o_slot[c->cur]),
+                       (const uint8_t*)(d + c->o_slot[c->forw]), d_pts, d_forw, d_status, (uint8_t*)(d + c->o_codes), (uint8_t*)(d + c->o_iters));
+    VILCHK(c->prof.mark(1, c->stream));
+    return VIL_OK;
+}
+
+int viltrack_stage::enqueue_detect(vtrack_ctx* c, const int n_max, const int* d_n, const float* d_pts, const int min_dist, const int max_cnt, const float quality,
+                                   Detection* out) {
+    char* d = c->d_mem;
+    const int W = c->cfg.width, H = c->cfg.height, MC = c->cfg.max_candidates;
+    const size_t WH = (size_t)W * H;
+    const uint8_t* img = (const uint8_t*)(d + c->o_slot[c->forw]);
+    int* d_hdr = (int*)(d + c->o_hdr); uint8_t* d_mask = (uint8_t*)(d + c->o_mask); float* d_eig = (float*)(d + c->o_eig);
+    unsigned* d_candeig = (unsigned*)(d + c->o_candeig); int* d_cstate = (int*)(d + c->o_cstate); int* d_clist = (int*)(d + c->o_clist);
+    VILCHK(hipMemsetAsync(d_hdr, 0, 4 * H_INTS, c->stream));
+    VILCHK(hipMemsetAsync(d_mask, 255, WH, c->stream));
+    unsigned long long* d_bitmap = (unsigned long long*)(d + c->o_bitmap); uint8_t* d_kept = (uint8_t*)(d + c->o_kept);
+    VILCHK(c->prof.mark(0, c->stream));
+    hipLaunchKernelGGL(k_track_mask, dim3(1), dim3(VT_ONE_WG), 0, c->stream, n_max, d_n, d_pts, min_dist, W, H, d_kept, d_hdr);
+    VILCHK(c->prof.mark(1, c->stream));
+    if (n_max) hipLaunchKernelGGL(k_track_paint, dim3(n_max), dim3(256), 0, c->stream, d_n, d_pts, d_kept, min_dist, W, H, d_mask);
+    VILCHK(c->prof.mark(2, c->stream));
+    hipLaunchKernelGGL(k_track_eig, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, c->stream, img, W, H, d_mask, d_eig, d_hdr);
+    VILCHK(c->prof.mark(3, c->stream));
+    hipLaunchKernelGGL(k_track_cand, dim3((unsigned)((WH + 255) / 256)), dim3(256), 0, c->stream, d_eig, d_mask, W, H, quality, MC, d_candeig, d_bitmap, d_cstate, d_clist, d_hdr);
+    VILCHK(c->prof.mark(4, c->stream));
+    for (int k = 0; k < VT_ROUNDS; ++k)
+        hipLaunchKernelGGL(k_track_round, dim3(std::min(1024, (MC + 3) / 4)), dim3(256), 0, c->stream, W, H, min_dist, MC, d_candeig, d_bitmap, d_cstate, d_clist, d_hdr);
+    VILCHK(c->prof.mark(5, c->stream));
+    hipLaunchKernelGGL(k_track_pick, dim3(1), dim3(VT_ONE_WG), 0, c->stream, W, H, min_dist, max_cnt, MC, d_candeig, d_bitmap, d_cstate, d_clist, (int*)(d + c->o_ulist),
+                       (int*)(d + c->o_plist), (float*)(d + c->o_new), d_hdr);
+    VILCHK(c->prof.mark(6, c->stream));
+    if (out) *out = {d_hdr, d_kept, (float*)(d + c->o_new)};
     return VIL_OK;
 }
 
@@ -553,9 +615,8 @@ int vtrack_profile_read(vtrack_ctx* c, int64_t* launches8, double* total_ms8) {
 int vtrack_push_image(vtrack_ctx* c, const uint8_t* gray, int32_t row_stride) {
     if (!c || !gray || row_stride < c->cfg.width) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    const int W = c->cfg.width, H = c->cfg.height;
-    for (int y = 0; y < H; ++y) memcpy(c->h_img + (size_t)y * W, gray + (size_t)y * row_stride, W);
-    VILCHK(hipMemcpyAsync(viltrack_stage::target(c).level0, c->h_img, (size_t)W * H, hipMemcpyHostToDevice, c->stream));
+    const uint8_t* staged = viltrack_stage::stage_image(c, gray, row_stride);
+    VILCHK(hipMemcpyAsync(viltrack_stage::target(c).level0, staged, (size_t)c->cfg.width * c->cfg.height, hipMemcpyHostToDevice, c->stream));
     return viltrack_stage::finish_push(c);
 }
 
@@ -565,14 +626,10 @@ int vtrack_track(vtrack_ctx* c, int32_t n, const float* cur_xy, float* forw_xy, 
     if (n) {
         VILCHK(hipSetDevice(c->device));
         char* d = c->d_mem;
-        const int L = c->cfg.max_level;
         memcpy(c->h_in, cur_xy, 8 * (size_t)n);
         VILCHK(hipMemcpyAsync(d + c->o_pts, c->h_in, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        VILCHK(c->prof.mark(0, c->stream));
-        hipLaunchKernelGGL(k_track_lk, dim3(n), dim3(64), 0, c->stream, n, L, (const int4*)(d + c->o_lvl), (const uint8_t*)(d + c->o_slot[c->cur]),
-                           (const uint8_t*)(d + c->o_slot[c->forw]), (const float*)(d + c->o_pts), (float*)(d + c->o_forw), (uint8_t*)(d + c->o_status), (uint8_t*)(d + c->o_codes),
-                           (uint8_t*)(d + c->o_iters));
-        VILCHK(c->prof.mark(1, c->stream));
+        const int st = viltrack_stage::enqueue_lk(c, n, nullptr, (const float*)(d + c->o_pts), (float*)(d + c->o_forw), (uint8_t*)(d + c->o_status));
+        if (st != VIL_OK) return st;
         const size_t st_off = c->o_status - c->o_forw;
         VILCHK(hipMemcpyAsync(c->h_out, d + c->o_forw, st_off + (size_t)n, hipMemcpyDeviceToHost, c->stream));
         VILCHK(hipStreamSynchronize(c->stream));
@@ -593,33 +650,14 @@ int vtrack_detect(vtrack_ctx* c, int32_t n_tracks, const float* tracks_xy, int32
         return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     char* d = c->d_mem;
-    const int W = c->cfg.width, H = c->cfg.height, MC = c->cfg.max_candidates;
-    const size_t WH = (size_t)W * H;
-    const uint8_t* img = (const uint8_t*)(d + c->o_slot[c->forw]);
-    int* d_hdr = (int*)(d + c->o_hdr); uint8_t* d_mask = (uint8_t*)(d + c->o_mask); float* d_eig = (float*)(d + c->o_eig);
-    unsigned* d_candeig = (unsigned*)(d + c->o_candeig); int* d_cstate = (int*)(d + c->o_cstate); int* d_clist = (int*)(d + c->o_clist);
+    const int MC = c->cfg.max_candidates;
+    int* d_hdr = (int*)(d + c->o_hdr);
     if (n_tracks) {
         memcpy(c->h_in, tracks_xy, 8 * (size_t)n_tracks);
         VILCHK(hipMemcpyAsync(d + c->o_pts, c->h_in, 8 * (size_t)n_tracks, hipMemcpyHostToDevice, c->stream));
     }
-    VILCHK(hipMemsetAsync(d_hdr, 0, 4 * H_INTS, c->stream));
-    VILCHK(hipMemsetAsync(d_mask, 255, WH, c->stream));
-    unsigned long long* d_bitmap = (unsigned long long*)(d + c->o_bitmap); uint8_t* d_kept = (uint8_t*)(d + c->o_kept); const float* d_pts = (const float*)(d + c->o_pts);
-    VILCHK(c->prof.mark(0, c->stream));
-    hipLaunchKernelGGL(k_track_mask, dim3(1), dim3(VT_ONE_WG), 0, c->stream, n_tracks, d_pts, min_dist, W, H, d_kept, d_hdr);
-    VILCHK(c->prof.mark(1, c->stream));
-    if (n_tracks) hipLaunchKernelGGL(k_track_paint, dim3(n_tracks), dim3(256), 0, c->stream, d_pts, d_kept, min_dist, W, H, d_mask);
-    VILCHK(c->prof.mark(2, c->stream));
-    hipLaunchKernelGGL(k_track_eig, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, c->stream, img, W, H, d_mask, d_eig, d_hdr);
-    VILCHK(c->prof.mark(3, c->stream));
-    hipLaunchKernelGGL(k_track_cand, dim3((unsigned)((WH + 255) / 256)), dim3(256), 0, c->stream, d_eig, d_mask, W, H, quality, MC, d_candeig, d_bitmap, d_cstate, d_clist, d_hdr);
-    VILCHK(c->prof.mark(4, c->stream));
-    for (int k = 0; k < VT_ROUNDS; ++k)
-        hipLaunchKernelGGL(k_track_round, dim3(std::min(1024, (MC + 3) / 4)), dim3(256), 0, c->stream, W, H, min_dist, MC, d_candeig, d_bitmap, d_cstate, d_clist, d_hdr);
-    VILCHK(c->prof.mark(5, c->stream));
-    hipLaunchKernelGGL(k_track_pick, dim3(1), dim3(VT_ONE_WG), 0, c->stream, W, H, min_dist, max_cnt, MC, d_candeig, d_bitmap, d_cstate, d_clist, (int*)(d + c->o_ulist),
-                       (int*)(d + c->o_plist), (float*)(d + c->o_new), d_hdr);
-    VILCHK(c->prof.mark(6, c->stream));
+    const int st = viltrack_stage::enqueue_detect(c, n_tracks, nullptr, (const float*)(d + c->o_pts), min_dist, max_cnt, quality, nullptr);
+    if (st != VIL_OK) return st;
     const size_t kept_off = c->o_kept - c->o_hdr, new_off = c->o_new - c->o_hdr;
     VILCHK(hipMemcpyAsync(c->h_out, d_hdr, new_off + 8 * (size_t)std::min(max_cnt, MC), hipMemcpyDeviceToHost, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));
