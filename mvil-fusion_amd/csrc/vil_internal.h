@@ -1,7 +1,10 @@
 // vil_internal.h -- entry points shared between the translation units of libvilsolve.so that are NOT part of the public
 // C-ABI (include/*.h): they take device pointers.
 #pragma once
+#include <cstdio>
 #include "../../include/vilsolve.h"
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[vilsolve] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return VIL_ERR_DEVICE; } } while (0)
 
 // LiDAR point factors that already live on the device, structure-of-arrays, all attached to window pose 0:
 //   plane_soa[q * plane_stride + f], q < 7 (cp n d) ; edge_soa[q * edge_stride + f], q < 9 (cp a b)

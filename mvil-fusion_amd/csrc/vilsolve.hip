@@ -15,15 +15,10 @@
 #include <thread>
 #include <array>
 #include <map>
-#include <memory>
-#include <pthread.h>
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types only: RCCL is bound at run time (dlopen) so that a process which already
-                         // carries an RCCL (PyTorch bundles one) never ends up with two copies
 
 #include "../../include/vilsolve_debug.h"
 #include "vil_internal.h"
+#include "vil_comm.hpp"
 #include "vil_tuning.hpp"
 #include "vil_coop.hpp"
 #include "vil_dev.hpp"
@@ -39,32 +34,7 @@
 const void* vil_k_solve_fn(int vis_ts);
 void vil_k_solve_launch(int vis_ts, unsigned grid, size_t lds, hipStream_t stream, const DevP& P, const SolveOpts& O, long long budget_ticks);
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[vilsolve] HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return VIL_ERR_DEVICE; } } while (0)
-
 namespace {
-
-struct RcclApi {
-    void* h = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    bool load() {
-        if (h) return true;
-        const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-        for (const char* n : names) { h = dlopen(n, RTLD_NOW | RTLD_NOLOAD); if (h) break; }     // reuse a copy that is already mapped
-        if (!h) for (const char* n : names) { h = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-        if (!h) return false;
-        GetUniqueId = (decltype(GetUniqueId))dlsym(h, "ncclGetUniqueId");
-        CommInitRank = (decltype(CommInitRank))dlsym(h, "ncclCommInitRank");
-        AllReduce = (decltype(AllReduce))dlsym(h, "ncclAllReduce");
-        AllGather = (decltype(AllGather))dlsym(h, "ncclAllGather");
-        CommDestroy = (decltype(CommDestroy))dlsym(h, "ncclCommDestroy");
-        return GetUniqueId && CommInitRank && AllReduce && AllGather && CommDestroy;
-    }
-};
-RcclApi g_rccl;
 
 // One device allocation per uploaded window: [tables | work space].  The tables (everything the caller hands over) are
 // assembled in a PINNED host image and go up in one DMA; the work space (partial records, systems, step vectors) exists on the
@@ -92,159 +62,6 @@ struct Arena {
 
 }  // namespace
 
-// In-process communicator: the contexts of ONE process (one host thread each) sum their buffers through device
-// memory.  Same call sites and the same deterministic result on every rank as the RCCL path; used where the ranks share
-// a process, and by the tests to run a sharded solve on a single device.
-struct LocalComm {
-    int n = 0;
-    pthread_barrier_t bar;
-    double* ptr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int err[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // per-rank status of the current collective: an error on one rank is an error on all (nobody is left at a barrier)
-    ~LocalComm() { if (n) pthread_barrier_destroy(&bar); }
-    // every rank posts its status, waits, and reads the worst one: collective error exits
-    int agree(int rank, int st) { err[rank] = st; pthread_barrier_wait(&bar); int w = 0; for (int r = 0; r < n; ++r) w = std::min(w, err[r]); pthread_barrier_wait(&bar); return w; }
-};
-struct PeerPtrs { const double* p[8]; int n; };
-
-// Multi-process exchange without RCCL (the per-iteration message is latency-bound; on the fully connected xGMI mesh a one-shot
-// "everybody writes to everybody, then sums locally" beats a ring): every rank owns an INBOX in its device memory -- world x 2 (parity of
-// the collective's sequence number) x cap doubles, then one flag per (source rank, parity), 64 bytes apart -- exported with hipIpcGetMemHandle
-// and opened by every peer.  A collective = k_ipc_push (my message into every inbox, a system-scope fence, then the flags) ->
-// k_ipc_wait (one workgroup spins until every source's flag carries the sequence number) -> k_ipc_sum (rank order: identical bits on every
-// rank).  Everything is in stream order and the sequence number lives in device memory: capturable in a hipGraph, nothing for the host to wait for.
-// Two parities suffice: a peer can only push collective i + 2 after it has summed i + 1, which needs MY push of i + 1, which I do after my sum of i.
-struct IpcComm {
-    int world = 0, rank = 0; size_t cap = 0;
-    bool ready = false;                       // every peer's handle is open (vil_comm_ipc_init): before that a collective would write through null inbox pointers
-    char* base = nullptr;                     // my allocation: [inbox | flags | seq | count]
-    void* peer_base[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // opened handles (my own: base)
-    size_t off_flags = 0, off_seq = 0;
-    double* inbox(int r) const { return (double*)peer_base[r]; }
-    int* flags(int r) const { return (int*)((char*)peer_base[r] + off_flags); }
-    int* seq() const { return (int*)(base + off_seq); }
-};
-struct IpcPtrs { double* inbox[8]; int* flags[8]; int world, rank; size_t cap; int* seq; int* count; };
-// sym = D > 0: the message starts with a symmetric D x D block (the reduced system S', both triangles filled with the same bits by the gather): only
-// its lower triangle travels, the sum writes both mirror images -- identical bits, D (D - 1) / 2 doubles less per rank pair (98 of 484 kB at K = 10)
-__device__ __forceinline__ bool sym_skip(size_t e, int sym) { if (!sym || e >= (size_t)sym * sym) return false; const int i = (int)(e / sym), j = (int)(e - (size_t)i * sym); return j > i; }
-__device__ __forceinline__ void sym_store(double* out, size_t e, int sym, double v) {
-    out[e] = v;
-    if (sym && e < (size_t)sym * sym) { const int i = (int)(e / sym), j = (int)(e - (size_t)i * sym); if (j < i) out[(size_t)j * sym + i] = v; }
-}
-// Owned segments of the per-iteration message [camera part | h_ll, b_l, 1/pivot, scale (L each) | e_A (13 L) | e_O (6 F)]: a landmark's entries are
-// non-zero on ONE rank, its owner (contiguous landmark / factor ranges, vil_shard_ranges) -- "sum over the ranks" of that part is "take the owner's value"
-// (x + 0 + ... + 0 = x: the same bits).  The library's own exchanges therefore move the camera part of every rank but only the OWNED slice of the landmark
-// arrays: per peer 103 + 380 / world kB instead of 390 kB at K = 10 / 1000 landmarks (150 kB at world = 8), and the summing kernel reads one inbox for them.
-struct OwnSeg { size_t cam; int Lp, n; int lb[9], fb[9]; };      // n = 0: a plain sum of everything (agreements; RCCL beyond eight ranks)
-__device__ __forceinline__ int seg_owner(const OwnSeg& S, size_t e) {          // -1: summed over all ranks
-    if (S.n == 0 || e < S.cam) return -1;
-    const size_t a = e - S.cam, Lp = (size_t)S.Lp;
-    const bool lm = a < 17 * Lp;
-    const int v = a < 4 * Lp ? (int)(a % Lp) : (lm ? (int)((a - 4 * Lp) / 13) : (int)((a - 17 * Lp) / 6));
-    const int* b = lm ? S.lb : S.fb;
-    int r = 0;
-    while (r + 1 < S.n && v >= b[r + 1]) ++r;
-    return r;
-}
-__global__ void k_ipc_push(const double* send, size_t cnt, IpcPtrs I, int sym, OwnSeg S) {
-    const int sq = *I.seq + 1, par = sq & 1;
-    const size_t off = ((size_t)I.rank * 2 + par) * I.cap;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
-        if (sym_skip(e, sym)) continue;
-        const int own = seg_owner(S, e);
-        if (own >= 0 && own != I.rank) continue;          // somebody else's landmark: zero here, nothing to send
-        const double v = send[e];
-        for (int r = 0; r < I.world; ++r) I.inbox[r][off + e] = v;
-    }
-    __threadfence_system();                   // this thread's stores have reached every peer ...
-    __syncthreads();
-    __shared__ int last;
-    if (threadIdx.x == 0) last = atomicAdd(I.count, 1) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (last && threadIdx.x == 0) {           // ... all blocks' have: the flags go out, the sequence number advances
-        __threadfence_system();
-        *I.count = 0;
-        for (int r = 0; r < I.world; ++r) __hip_atomic_store(I.flags[r] + 16 * (I.rank * 2 + par), sq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        *I.seq = sq;
-    }
-}
-__global__ void k_ipc_wait(IpcPtrs I) {
-    const int sq = *I.seq, par = sq & 1, t = threadIdx.x;       // (k_ipc_push of this collective has advanced it: same stream)
-    if (t < I.world) while (__hip_atomic_load(I.flags[I.rank] + 16 * (t * 2 + par), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != sq) __builtin_amdgcn_s_sleep(8);
-}
-__global__ void k_ipc_sum(double* out, size_t cnt, IpcPtrs I, int sym, OwnSeg S) {
-    const int par = *I.seq & 1;
-    const double* in = I.inbox[I.rank];
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
-        if (sym_skip(e, sym)) continue;
-        const int own = seg_owner(S, e);
-        double s = 0;
-        if (own >= 0) s = __builtin_nontemporal_load(in + ((size_t)own * 2 + par) * I.cap + e);                        // the owner's entry (everybody else's is zero and did not travel)
-        else for (int r = 0; r < I.world; ++r) s += __builtin_nontemporal_load(in + ((size_t)r * 2 + par) * I.cap + e);      // written by peers: not through a stale cache line
-        sym_store(out, e, sym, s);
-    }
-}
-__global__ void k_sum_peers(double* out, PeerPtrs pp, size_t cnt, int sym, OwnSeg S) {
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
-        if (sym_skip(e, sym)) continue;
-        const int own = seg_owner(S, e);
-        double s = 0;
-        if (own >= 0) s = pp.p[own][e];
-        else for (int r = 0; r < pp.n; ++r) s += pp.p[r][e];     // rank order: identical bits on every rank
-        sym_store(out, e, sym, s);
-    }
-}
-
-// The same slim message for RCCL ("[upper(S), g, cost]", ~100 kB): the per-iteration set is PACKED into M = [lower triangle of S' | g, b_c, diag | cost]
-// (D (D + 1) / 2 + 3 D + 4 doubles, summed by ONE ncclAllReduce) and G = this rank's slice of the landmark arrays [h_ll, b_l, 1/pivot, scale | e_A | e_O], padded
-// to the largest slice (ONE ncclAllGather: a landmark's entries live on its owner only, so the sum over ranks is the owner's value -- nothing to add), and
-// UNPACKED into set 1 with both mirror images of S'.  At K = 10 / 1000 landmarks / world 8 RCCL moves 103 + 48 kB per rank instead of all-reducing 484 kB.
-// staging (doubles): [M camS | G gmax | Msum camS | Gall world x gmax]; pack / unpack do not know the transport -- the tests run them over the in-process
-// communicator with k_slim_emul standing in for the two RCCL calls (vil_debug_set_slim_emul), on 2 / 3 / 8 ranks of one device.
-struct SlimLay { int D, Lp, n, rank; size_t cam, camS, gmax, span; int lb[9], fb[9]; };
-__device__ __forceinline__ size_t slim_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }
-// position of set entry e (e >= cam) inside its owner's slice; *owner receives the rank
-__device__ __forceinline__ size_t slim_slot(const SlimLay& Y, size_t e, int* owner) {
-    const size_t a = e - Y.cam, Lp = (size_t)Y.Lp;
-    const bool lm = a < 17 * Lp;
-    const int v = a < 4 * Lp ? (int)(a % Lp) : (lm ? (int)((a - 4 * Lp) / 13) : (int)((a - 17 * Lp) / 6));
-    const int* b = lm ? Y.lb : Y.fb;
-    if (v >= b[Y.n]) { *owner = -1; return 0; }      // padding of an empty array (Lp = max(L, 1), Fp = max(n_vis, 1) with L or n_vis = 0): nobody owns it, it stays zero
-    int r = 0;
-    while (r + 1 < Y.n && v >= b[r + 1]) ++r;
-    *owner = r;
-    const size_t nL = (size_t)(Y.lb[r + 1] - Y.lb[r]);
-    if (a < 4 * Lp) return (a / Lp) * nL + (size_t)(v - Y.lb[r]);
-    if (lm) return 4 * nL + (a - 4 * Lp) - 13 * (size_t)Y.lb[r];
-    return 17 * nL + (a - 17 * Lp) - 6 * (size_t)Y.fb[r];
-}
-__global__ void k_slim_pack(const double* set0, double* M, double* G, SlimLay Y) {
-    const size_t DD = (size_t)Y.D * Y.D, trin = (size_t)Y.D * (Y.D + 1) / 2;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < Y.span; e += (size_t)gridDim.x * blockDim.x) {
-        if (e < DD) { const int i = (int)(e / Y.D), j = (int)(e - (size_t)i * Y.D); if (j <= i) M[slim_tri(i, j)] = set0[e]; }
-        else if (e < Y.cam) M[trin + (e - DD)] = set0[e];
-        else { int r; const size_t g = slim_slot(Y, e, &r); if (r == Y.rank) G[g] = set0[e]; }
-    }
-}
-__global__ void k_slim_unpack(double* set1, const double* Msum, const double* Gall, SlimLay Y) {
-    const size_t DD = (size_t)Y.D * Y.D, trin = (size_t)Y.D * (Y.D + 1) / 2;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < Y.span; e += (size_t)gridDim.x * blockDim.x) {
-        double v;
-        if (e < DD) { const int i = (int)(e / Y.D), j = (int)(e - (size_t)i * Y.D); v = Msum[slim_tri(max(i, j), min(i, j))]; }
-        else if (e < Y.cam) v = Msum[trin + (e - DD)];
-        else { int r; const size_t g = slim_slot(Y, e, &r); v = r >= 0 ? Gall[(size_t)r * Y.gmax + g] : 0.0; }
-        set1[e] = v;
-    }
-}
-// stand-in for ncclAllReduce(M -> Msum) + ncclAllGather(G -> Gall) over the in-process communicator (tests): pp.p[r] = rank r's staging buffer
-__global__ void k_slim_emul(double* Msum, double* Gall, PeerPtrs pp, SlimLay Y) {
-    const size_t tot = Y.camS + (size_t)pp.n * Y.gmax;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
-        if (e < Y.camS) { double a = 0; for (int r = 0; r < pp.n; ++r) a += pp.p[r][e]; Msum[e] = a; }
-        else { const size_t q = e - Y.camS; const int r = (int)(q / Y.gmax); Gall[q] = pp.p[r][Y.camS + (q - (size_t)r * Y.gmax)]; }
-    }
-}
-
 #define VIL_MAX_CHUNK 24       // iterations enqueued without a host round trip (the first solve of an upload: vil_solve_resident); vil_profile_enable sizes its events for it
 #define VIL_CHC_MAX 16384      // entries of the chain workgroup's gather table (K = 20: ~7000)
 #define VIL_SFLAG_MAX 4096      // sweep workgroups a one-launch iteration may have (configs[2]: ~600)
@@ -257,8 +74,9 @@ struct Structure {
     int n_sweep = 0, n_reduce = 0, n_reduce_po = 0, n_gather_m = 0, cap_fused = -1;       // workgroups: sweep roles, k_reduce (all / pose-only gather), gather of the merged launch; cap_fused: of k_iter, at lds_iter, the device holds at once (vil_solve_batch)
 };
 struct vil_ctx {
-    int device = 0, rank = 0, world = 1;
+    int device = 0;
     hipStream_t stream = nullptr;
+    Comm comm;                     // multi-GPU: rank, world, the transport and the owner table of the per-iteration message (vil_comm.hpp)
     Arena ar;
     hipEvent_t dep_ev = nullptr;                           // orders the solve after a producer stream (vil_solve_device_lidar)
     hipEvent_t up_ev = nullptr; bool up_pending = false;   // the DMA out of the pinned image must finish before the image is rewritten
@@ -293,14 +111,6 @@ struct vil_ctx {
     size_t marg_ws_bytes = 0;
     size_t h_pin_bytes = 0;
     std::vector<int> prior_joff;
-    ncclComm_t comm = nullptr;     // RCCL communicator over xGMI (world > 1)
-    std::shared_ptr<struct LocalComm> lcomm;   // in-process communicator (vil_comm_init_local)
-    std::shared_ptr<struct IpcComm> ipc;       // multi-process peer-buffer exchange (vil_comm_ipc_export / vil_comm_ipc_init)
-    bool has_comm() const { return comm != nullptr || lcomm != nullptr || ipc != nullptr; }
-    double* lc_tmp = nullptr; size_t lc_cap = 0;
-    double* ipc_tmp = nullptr;
-    double* slim_buf = nullptr; size_t slim_cap = 0; bool slim_emul = false;      // staging of the packed per-iteration message (RCCL; vil_debug_set_slim_emul)
-    bool slim() const { return own.n > 0 && world > 1 && (comm != nullptr || (slim_emul && lcomm != nullptr)); }
     bool sharded = false;          // the resident problem is this rank's shard of the factor set
     // hipGraph of a chunk of iterations, reused by repeated solves of one upload (key: chunk length, options)
     struct ChunkGraph { int n; SolveOpts so; hipGraphExec_t exec; };
@@ -319,8 +129,6 @@ struct vil_ctx {
     int launch_mode = 0;           // vil_debug_set_launch_mode: 0 = the library's choice, 1 = no merged launch, 2 = no chain workgroup, 3 = sweep + merged gather / step launch (no one-launch iteration)
     int last_live = 5;             // live sweep launches of the previous solve (sizes the first launch chunk)
     int recent_live[8] = {5, 5, 5, 5, 5, 5, 5, 5}; int recent_at = 0;      // ... of the last eight solves: the first solve of an upload (a tracker's image) is sized by their maximum
-    int lm_b = 0, lm_e = 0;        // owned landmark range
-    OwnSeg own = {0, 0, 0, {0}, {0}};      // every rank's landmark / factor range in the per-iteration message (sharded windows)
     // ---- window residency across frames (vil_lidar_*, vil_set_gauge_fix, vil_marginalize_resident) --------------------------------
     struct Slab { int np, ne, slot; int np_all, ne_all; };      // np_all / ne_all: the frame's points BEFORE a communicator's slicing (the same on every rank)
     std::vector<Slab> slabs;       // window order: slab i <-> pose K - count + i
@@ -495,7 +303,7 @@ int vil_create(const vil_device_cfg* cfg, vil_ctx** out) {
     if (cfg->device < 0 || cfg->device >= ndev) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(cfg->device));
     vil_ctx* c = new vil_ctx();
-    c->device = cfg->device; c->rank = cfg->rank; c->world = cfg->world > 0 ? cfg->world : 1;
+    c->device = cfg->device; c->comm.rank = cfg->rank; c->comm.world = cfg->world > 0 ? cfg->world : 1;
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipMalloc(&c->d_status, sizeof(int)));
     HIPCHK(hipMemset(c->d_status, 0, sizeof(int)));
@@ -515,7 +323,7 @@ void vil_destroy(vil_ctx* c) {
     for (auto& e : c->ev_mid) hipEventDestroy(e);
     for (auto& e : c->ev_coll) hipEventDestroy(e);
     for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
-    if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
+    c->comm.release(c->device);
     if (c->ar.d) hipFree(c->ar.d);
     if (c->ar.h) hipHostFree(c->ar.h);
     if (c->up_ev) hipEventDestroy(c->up_ev);
@@ -526,13 +334,9 @@ void vil_destroy(vil_ctx* c) {
     if (c->h_mirror) hipHostFree(c->h_mirror);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->marg_ws) hipFree(c->marg_ws);
-    if (c->lc_tmp) hipFree(c->lc_tmp);
     if (c->d_imu_perm) hipFree(c->d_imu_perm);
     for (auto& ct : c->chtabs) { if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h); if (ct.ev) hipEventDestroy(ct.ev); }
-    if (c->ipc_tmp) hipFree(c->ipc_tmp);
-    if (c->slim_buf) hipFree(c->slim_buf);
     if (c->d_prof) hipFree(c->d_prof);
-    if (c->ipc) { for (int r = 0; r < c->ipc->world; ++r) if (r != c->ipc->rank && c->ipc->peer_base[r]) hipIpcCloseMemHandle(c->ipc->peer_base[r]); if (c->ipc->base) hipFree(c->ipc->base); c->ipc.reset(); }
     if (c->d_pl) hipFree(c->d_pl);
     if (c->d_ed) hipFree(c->d_ed);
     if (c->d_lstage) hipFree(c->d_lstage);
@@ -758,14 +562,6 @@ struct WinSrc {
     int lb, le, f0, n_vis_all;       // sharded (gp != null): this rank keeps the factors of landmarks [lb, le), the first of which is factor f0 of the n_vis_all of the window
 };
 
-// first landmark whose factor prefix reaches r / world of the total (lms: factor prefix per landmark, L + 1 entries) -- THE sharding rule of the visual factors
-static int shard_cut(const std::vector<int>& lms, int L, int r, int world) {
-    if (r <= 0) return 0;
-    if (r >= world) return L;
-    const long long target = (long long)lms[L] * r / world;
-    return std::min((int)(std::lower_bound(lms.begin(), lms.end(), (int)target) - lms.begin()), L);
-}
-
 // ---- upload_impl, stage by stage.  Every table goes into ONE pinned image in the order of its put(): the arena layout is that order.
 struct ImageBuilder {
     Arena& ar;
@@ -986,10 +782,10 @@ static size_t upload_workspace(vil_ctx* c, ImageBuilder& im, const WinSrc* ws, c
     const size_t ar_cam = ((size_t)D * D + 3 * (size_t)D + 3 + 1) & ~size_t(1);
     c->span = ar_cam + 4 * Lp + 13 * Lp + 6 * Fp;
     for (int q = 0; q < 2; ++q) im.put(nullptr, 8 * c->span, (void**)&P.sys[q].ar);
-    P.rank = sharded ? c->rank : 0; P.world = sharded ? c->world : 1;
+    P.rank = sharded ? c->comm.rank : 0; P.world = sharded ? c->comm.world : 1;
     for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
     c->graphs.clear(); c->solves_since_upload = 0;
-    c->sharded = sharded && c->world > 1;
+    c->sharded = sharded && c->comm.world > 1;
     // multi-GPU plumbing (set 0 = this rank's partial system, all-reduced into set 1, which the step kernel reads); vil_debug_set_split
     // runs it on a single rank (tests)
     c->split = c->sharded || c->force_split;
@@ -1344,187 +1140,41 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
     return VIL_OK;
 }
 
-static int comm_agree(vil_ctx* c, int st);
-static int ensure_pin(vil_ctx* c, size_t bytes);
-
 // rank r keeps the visual factors of its landmark range, a contiguous slice of the LiDAR points, and
 // (rank 0 only) the IMU / prior / ICP / LPS factors.  Landmark indices and the state stay global.
 static int upload_sharded(vil_ctx* c, const vil_problem* p, const vil_state* s) {
-    int32_t lb, le, eb, ee, pb, pe;
-    int st = validate(p, s);                     // vil_shard_ranges indexes with vis_l: check the tables first
-    if (st == VIL_OK) st = vil_shard_ranges(p, c->rank, c->world, &lb, &le, &eb, &ee, &pb, &pe);
-    if (st != VIL_OK) return comm_agree(c, st);  // every rank sees the same problem, but stay collective anyway
+    Comm& cm = c->comm;
+    int st = validate(p, s);                     // the factor prefix indexes with vis_l: check the tables first
+    if (st != VIL_OK) return cm.agree(c->stream, st);  // every rank sees the same problem, but stay collective anyway
+    std::vector<int> lms(p->L + 1, 0);           // factor prefix per landmark (factors sorted by landmark): the rule of vil_shard_ranges
+    for (int f = 0; f < p->n_vis; ++f) lms[p->vis_l[f] + 1]++;
+    for (int l = 0; l < p->L; ++l) lms[l + 1] += lms[l];
+    cm.set_owners(lms, p->L, p->K);
+    const int f0 = lms[shard_cut(lms, p->L, cm.rank, cm.world)], f1 = lms[shard_cut(lms, p->L, cm.rank + 1, cm.world)];
     vil_problem q = *p;
-    int f0 = 0, f1 = 0;
-    for (int f = 0; f < p->n_vis; ++f) { if (p->vis_l[f] < lb) f0 = f + 1; if (p->vis_l[f] < le) f1 = f + 1; }
     q.n_vis = f1 - f0; q.vis_i = p->vis_i + f0; q.vis_j = p->vis_j + f0; q.vis_l = p->vis_l + f0; q.vis_const = p->vis_const + (size_t)f0 * 14;
     if (p->n_plane == VIL_LIDAR_RESIDENT && p->n_edge == VIL_LIDAR_RESIDENT) { /* the slabs of this context already hold this rank's slice of every frame (vil_lidar_push) */ }
     else {
+        const int eb = (int)((long long)p->n_edge * cm.rank / cm.world), ee = (int)((long long)p->n_edge * (cm.rank + 1) / cm.world);
+        const int pb = (int)((long long)p->n_plane * cm.rank / cm.world), pe = (int)((long long)p->n_plane * (cm.rank + 1) / cm.world);
         q.n_edge = ee - eb; q.edge_pose = p->edge_pose + eb; q.edge_const = p->edge_const + (size_t)eb * 9;
         q.n_plane = pe - pb; q.plane_pose = p->plane_pose + pb; q.plane_const = p->plane_const + (size_t)pb * 7;
     }
-    if (c->rank != 0) { q.n_imu = 0; q.n_icp = 0; q.n_lps = 0; q.prior.n = 0; q.prior.nblk = 0; }
-    c->lm_b = lb; c->lm_e = le;
-    {   // who owns which slice of the landmark arrays of the message (the same arithmetic on every rank)
-        OwnSeg& S = c->own; memset(&S, 0, sizeof S);
-        S.n = c->world <= 8 ? c->world : 0; S.Lp = std::max(p->L, 1);      // (more than eight ranks: RCCL only, which sums the whole set -- n = 0)
-        for (int r = 0; r < S.n; ++r) {
-            int32_t b = 0; vil_shard_ranges(p, r, c->world, &b, nullptr, nullptr, nullptr, nullptr, nullptr);
-            S.lb[r] = b; int fb = 0; for (int f = 0; f < p->n_vis; ++f) if (p->vis_l[f] < b) fb = f + 1;
-            S.fb[r] = fb;
-        }
-        S.lb[S.n] = p->L; S.fb[S.n] = p->n_vis;
-        const int D = 15 * p->K + 7;
-        S.cam = ((size_t)D * D + 3 * (size_t)D + 3 + 1) & ~size_t(1);
-    }
-    st = comm_agree(c, upload_impl(c, &q, s, true, nullptr, p, f0));       // e.g. rank 0's IMU set-up failed: every rank reports it
+    if (cm.rank != 0) { q.n_imu = 0; q.n_icp = 0; q.n_lps = 0; q.prior.n = 0; q.prior.nblk = 0; }
+    st = cm.agree(c->stream, upload_impl(c, &q, s, true, nullptr, p, f0));       // e.g. rank 0's IMU set-up failed: every rank reports it
     if (st != VIL_OK) c->uploaded = false;
     return st;
 }
 
 static int upload_window(vil_ctx* c, const vil_problem* p, const vil_state* s, bool check_setup) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    if (c->ipc && c->world > 1 && !c->ipc->ready) return VIL_ERR_COMM;             // vil_comm_ipc_export without vil_comm_ipc_init
-    const int st = (c->world > 1 && c->has_comm()) ? upload_sharded(c, p, s)      // a world > 1 context without a communicator works un-sharded
+    if (c->comm.world > 1 && !c->comm.ready()) return VIL_ERR_COMM;             // vil_comm_ipc_export without vil_comm_ipc_init
+    const int st = (c->comm.sharded()) ? upload_sharded(c, p, s)      // a world > 1 context without a communicator works un-sharded
                                                            : upload_impl(c, p, s, false, nullptr, nullptr, 0, check_setup);
     if (st == VIL_OK) c->resident_kind = 1;
     return st;
 }
 int vil_upload(vil_ctx* c, const vil_problem* p, const vil_state* s) { return upload_window(c, p, s, true); }
-
-// sum over the ranks of the communicator, in stream order: recv = sum of every rank's send (recv may be send)
-static const OwnSeg kNoSeg = {0, 0, 0, {0}, {0}};
-static int ipc_all_reduce(vil_ctx* c, const double* send, double* recv, size_t cnt, int sym = 0, const OwnSeg& seg = kNoSeg) {
-    IpcComm* ic = c->ipc.get();
-    if (!ic->ready) return VIL_ERR_COMM;                // vil_comm_ipc_export without vil_comm_ipc_init: the peers' inboxes are not mapped yet
-    if (cnt > ic->cap) return VIL_ERR_UNSUPPORTED;      // the inbox was sized at vil_comm_ipc_export
-    IpcPtrs I; memset(&I, 0, sizeof I);
-    for (int r = 0; r < ic->world; ++r) { I.inbox[r] = ic->inbox(r); I.flags[r] = ic->flags(r); }
-    I.world = ic->world; I.rank = ic->rank; I.cap = ic->cap; I.seq = ic->seq(); I.count = ic->seq() + 16;
-    const unsigned nb = (unsigned)std::min<size_t>(128, (cnt + 255) / 256);
-    hipLaunchKernelGGL(k_ipc_push, dim3(nb), dim3(256), 0, c->stream, send, cnt, I, sym, seg);
-    hipLaunchKernelGGL(k_ipc_wait, dim3(1), dim3(64), 0, c->stream, I);
-    hipLaunchKernelGGL(k_ipc_sum, dim3(nb), dim3(256), 0, c->stream, recv, cnt, I, sym, seg);
-    return VIL_OK;
-}
-static SlimLay slim_layout(const vil_ctx* c) {
-    SlimLay Y; memset(&Y, 0, sizeof Y);
-    const OwnSeg& S = c->own;
-    Y.D = c->D; Y.Lp = S.Lp; Y.n = S.n; Y.rank = c->rank; Y.cam = S.cam; Y.span = c->span;
-    Y.camS = ((size_t)Y.D * (Y.D + 1) / 2 + (S.cam - (size_t)Y.D * Y.D) + 1) & ~size_t(1);
-    for (int r = 0; r <= S.n; ++r) { Y.lb[r] = S.lb[r]; Y.fb[r] = S.fb[r]; }
-    for (int r = 0; r < S.n; ++r) Y.gmax = std::max(Y.gmax, (size_t)17 * (S.lb[r + 1] - S.lb[r]) + (size_t)6 * (S.fb[r + 1] - S.fb[r]));
-    Y.gmax = (Y.gmax + 2) & ~size_t(1);
-    return Y;
-}
-// the per-iteration collective as a packed message: pack -> all-reduce of M + all-gather of the owners' slices -> unpack (see SlimLay)
-static int slim_all_reduce(vil_ctx* c, const double* send, double* recv) {
-    const SlimLay Y = slim_layout(c);
-    const size_t need = 2 * Y.camS + (size_t)(1 + c->world) * Y.gmax;
-    LocalComm* lc = c->comm ? nullptr : c->lcomm.get();
-    int st = VIL_OK;
-    if (need > c->slim_cap) {
-        if (c->slim_buf) hipFree(c->slim_buf);
-        c->slim_buf = nullptr; c->slim_cap = 0;
-        if (hipMalloc(&c->slim_buf, 8 * need) == hipSuccess) { c->slim_cap = need; if (hipMemsetAsync(c->slim_buf, 0, 8 * need, c->stream) != hipSuccess) st = VIL_ERR_DEVICE; }
-        else st = VIL_ERR_DEVICE;
-        if (st != VIL_OK && !lc) return st;          // (in-process ranks carry a failure to the agreement point below)
-    }
-    double* M = c->slim_buf; double* G = M + Y.camS; double* Msum = G + Y.gmax; double* Gall = Msum + Y.camS;
-    const unsigned nb = (unsigned)std::min<size_t>(256, (Y.span + 255) / 256);
-    if (st == VIL_OK) hipLaunchKernelGGL(k_slim_pack, dim3(nb), dim3(256), 0, c->stream, send, M, G, Y);
-    if (!lc) {
-        if (g_rccl.AllReduce(M, Msum, Y.camS, ncclDouble, ncclSum, c->comm, c->stream) != ncclSuccess) return VIL_ERR_COMM;
-        if (g_rccl.AllGather(G, Gall, Y.gmax, ncclDouble, c->comm, c->stream) != ncclSuccess) return VIL_ERR_COMM;
-    } else {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        lc->ptr[c->rank] = c->slim_buf;
-        st = lc->agree(c->rank, st);                          // every rank's M and G are complete and published
-        if (st != VIL_OK) return st;
-        PeerPtrs pp; pp.n = lc->n;
-        for (int r = 0; r < 8; ++r) pp.p[r] = r < lc->n ? lc->ptr[r] : nullptr;
-        hipLaunchKernelGGL(k_slim_emul, dim3(nb), dim3(256), 0, c->stream, Msum, Gall, pp, Y);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        st = lc->agree(c->rank, st);                          // every rank has read every staging buffer
-        if (st != VIL_OK) return st;
-    }
-    hipLaunchKernelGGL(k_slim_unpack, dim3(nb), dim3(256), 0, c->stream, recv, (const double*)Msum, (const double*)Gall, Y);
-    return VIL_OK;
-}
-static int all_reduce2(vil_ctx* c, const double* send, double* recv, size_t cnt, int sym = 0, const OwnSeg& seg = kNoSeg) {
-    if (c->ipc) return ipc_all_reduce(c, send, recv, cnt, sym, seg);
-    if (seg.n > 0 && sym > 0 && cnt == c->span && c->slim()) return slim_all_reduce(c, send, recv);
-    if (c->comm) return g_rccl.AllReduce(send, recv, cnt, ncclDouble, ncclSum, c->comm, c->stream) == ncclSuccess ? VIL_OK : VIL_ERR_COMM;
-    if (c->lcomm) {
-        LocalComm* lc = c->lcomm.get();
-        int st = VIL_OK;
-        const bool inplace = send == recv;
-        if (inplace && cnt > c->lc_cap) { if (c->lc_tmp) hipFree(c->lc_tmp); c->lc_tmp = nullptr; c->lc_cap = 0; if (hipMalloc(&c->lc_tmp, 8 * cnt) == hipSuccess) c->lc_cap = cnt; else st = VIL_ERR_DEVICE; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        lc->ptr[c->rank] = const_cast<double*>(send);
-        st = lc->agree(c->rank, st);                          // all buffers are complete and published (or somebody failed)
-        if (st != VIL_OK) return st;
-        PeerPtrs pp; pp.n = lc->n;
-        for (int r = 0; r < 8; ++r) pp.p[r] = r < lc->n ? lc->ptr[r] : nullptr;
-        hipLaunchKernelGGL(k_sum_peers, dim3((unsigned)std::min<size_t>(256, (cnt + 255) / 256)), dim3(256), 0, c->stream, inplace ? c->lc_tmp : recv, pp, cnt, sym, seg);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        st = lc->agree(c->rank, st);                          // every rank has read every buffer
-        if (st != VIL_OK) return st;
-        if (inplace) HIPCHK(hipMemcpyAsync(recv, c->lc_tmp, 8 * cnt, hipMemcpyDeviceToDevice, c->stream));
-        return VIL_OK;
-    }
-    if (send != recv) HIPCHK(hipMemcpyAsync(recv, send, 8 * cnt, hipMemcpyDeviceToDevice, c->stream));     // a single rank (VIL_FORCE_SPLIT)
-    return VIL_OK;
-}
-static int all_reduce(vil_ctx* c, double* buf, size_t cnt) {
-    if (c->ipc) return ipc_all_reduce(c, buf, buf, cnt);      // (push reads, sum writes: different kernels, stream order)
-    if (c->comm) return g_rccl.AllReduce(buf, buf, cnt, ncclDouble, ncclSum, c->comm, c->stream) == ncclSuccess ? VIL_OK : VIL_ERR_COMM;
-    if (c->lcomm) {
-        // every HIP failure is carried to the next agreement point instead of returning past a barrier the other ranks wait at
-        LocalComm* lc = c->lcomm.get();
-        int st = VIL_OK;
-        if (cnt > c->lc_cap) { if (c->lc_tmp) hipFree(c->lc_tmp); c->lc_tmp = nullptr; c->lc_cap = 0; if (hipMalloc(&c->lc_tmp, 8 * cnt) == hipSuccess) c->lc_cap = cnt; else st = VIL_ERR_DEVICE; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        lc->ptr[c->rank] = buf;
-        st = lc->agree(c->rank, st);                          // all buffers are complete and published (or somebody failed)
-        if (st != VIL_OK) return st;
-        PeerPtrs pp; pp.n = lc->n;
-        for (int r = 0; r < 8; ++r) pp.p[r] = r < lc->n ? lc->ptr[r] : nullptr;
-        hipLaunchKernelGGL(k_sum_peers, dim3((unsigned)std::min<size_t>(256, (cnt + 255) / 256)), dim3(256), 0, c->stream, c->lc_tmp, pp, cnt, 0, kNoSeg);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) st = VIL_ERR_DEVICE;
-        st = lc->agree(c->rank, st);                          // every rank has read every buffer
-        if (st != VIL_OK) return st;
-        HIPCHK(hipMemcpyAsync(buf, c->lc_tmp, 8 * cnt, hipMemcpyDeviceToDevice, c->stream));
-    }
-    return VIL_OK;
-}
-
-// the ranks of a communicator agree on a status (the worst one): a rank-asymmetric failure -- only rank 0 holds the IMU / prior
-// factors whose set-up can fail -- must not leave the other ranks waiting in the first collective of the solve
-static int comm_agree(vil_ctx* c, int st) {
-    if (c->lcomm) return c->lcomm->agree(c->rank, st);
-    if (c->ipc) {                                          // every rank's status in its own slot of a world-long message: the worst one wins
-        const int w = c->ipc->world;
-        if (ensure_pin(c, 8 * 64) != VIL_OK) return VIL_ERR_DEVICE;
-        double* h = c->h_pin; for (int r = 0; r < w; ++r) h[r] = r == c->ipc->rank ? (double)st : 0.0;
-        if (!c->ipc_tmp && hipMalloc(&c->ipc_tmp, 8 * 64) != hipSuccess) return VIL_ERR_DEVICE;
-        if (hipMemcpyAsync(c->ipc_tmp, h, 8 * (size_t)w, hipMemcpyHostToDevice, c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        if (ipc_all_reduce(c, c->ipc_tmp, c->ipc_tmp + 32, (size_t)w) != VIL_OK) return VIL_ERR_COMM;
-        if (hipMemcpyAsync(h + 32, c->ipc_tmp + 32, 8 * (size_t)w, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        int worst = 0; for (int r = 0; r < w; ++r) worst = std::min(worst, (int)h[32 + r]);
-        return worst;
-    }
-    if (c->comm) {
-        int* h = c->h_word + 4; *h = st;
-        if (hipMemcpyAsync(c->d_status, h, sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        if (g_rccl.AllReduce(c->d_status, c->d_status, 1, ncclInt, ncclMin, c->comm, c->stream) != ncclSuccess) return VIL_ERR_COMM;
-        if (hipMemcpyAsync(h, c->d_status, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return VIL_ERR_DEVICE;
-        return *h;
-    }
-    return st;
-}
 
 // Multi-GPU: ONE collective per trust-region iteration.  Every rank sweeps its shard into set 0 -- the reduced camera
 // system of its factors plus the landmark arrays (h_ll, b_l, 1/pivot, scale, e_l) of the landmarks it owns, zeros elsewhere -- the
@@ -1574,7 +1224,7 @@ static int launch_reduce_step(vil_ctx* c, const SolveOpts& so, bool step, hipEve
     }
     if (ev_mid) hipEventRecord(ev_mid, c->stream);
     if (c->split) {                                    // the one collective of the iteration
-        const int st = all_reduce2(c, c->P.sys[0].ar, c->P.sys[1].ar, c->span, c->D, c->own);      // (S' first: its lower triangle travels; landmark arrays: the owners' slices)
+        const int st = c->comm.sum(c->stream, c->P.sys[0].ar, c->P.sys[1].ar, c->span, c->D, true, c->span);      // (S' first: its lower triangle travels; landmark arrays: the owners' slices)
         if (st != VIL_OK) return st;
     }
     if (ev_coll) hipEventRecord(ev_coll, c->stream);
@@ -1665,7 +1315,7 @@ static int first_chunk(const vil_ctx* c, bool fused) {
 // communicator synchronises on the host.  Polling the finished solve's mirror works for everything that is in stream order.
 static bool may_replay(vil_ctx* c, const Attempt& a) {
     if (c->use_graph < 0) { const char* ev = VIL_TUNE_ENV("VIL_GRAPH"); c->use_graph = ev ? atoi(ev) : 1; }
-    const bool no_graph = c->split && !c->ipc;
+    const bool no_graph = c->split && !c->comm.capturable();
     return c->use_graph && c->solves_since_upload > 0 && !c->profiling && !no_graph && !a.direct && !a.persist();      // (direct: a retry, or a solve with a debug hook in its parameter block)
 }
 // The hipGraph of a chunk of n iterations and its k_finish: the cached one of this (n, options), or a fresh capture.  *exec == nullptr: launch directly
@@ -1725,7 +1375,7 @@ static int enqueue_chunk(vil_ctx* c, const Attempt& a, int n) {
         launch_sweep(c, a.so);
         if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * q + 1], c->stream));
         const int st = launch_reduce_step(c, a.so, true, c->profiling ? c->ev_mid[q] : nullptr, c->profiling ? c->ev_coll[q] : nullptr);
-        if (st != VIL_OK) return st;          // a failed collective fails on every rank (all_reduce): nobody is left waiting
+        if (st != VIL_OK) return st;          // a failed collective fails on every rank (Comm::sum): nobody is left waiting
     }
     if (c->profiling) HIPCHK(hipEventRecord(c->ev[2 * n], c->stream));
     hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, view(c, 0), -1);      // the write-out of a solve that ended in the chunk's last iteration
@@ -1737,7 +1387,7 @@ static int enqueue_chunk(vil_ctx* c, const Attempt& a, int n) {
 // Leaves *c->h_ctl filled; *via_mirror is set when it came through the mirror.
 static int await_result(vil_ctx* c, bool* via_mirror) {
     bool polled = false;
-    if (c->d_hseq && !c->profiling && !(c->split && c->lcomm != nullptr)) {
+    if (c->d_hseq && !c->profiling && !(c->split && c->comm.host_synchronised())) {
         volatile int* seq = (volatile int*)(c->h_mirror + sizeof(Ctl));
         const int gen = c->solve_gen;
         const auto tp0 = std::chrono::steady_clock::now();
@@ -2013,7 +1663,7 @@ int vil_solve(vil_ctx* c, const vil_problem* p, vil_state* s, const vil_options*
 int vil_solve_device_lidar(vil_ctx* c, const vil_problem* p, const vil_device_lidar* dl, void* producer_stream, vil_state* s, const vil_options* o, vil_summary* sum) {
     if (!c || !p || !dl || !s || !o || !sum) return VIL_ERR_INVALID_ARGUMENT;
     if ((p->n_plane > 0 && (!dl->plane_soa || dl->plane_stride < p->n_plane)) || (p->n_edge > 0 && (!dl->edge_soa || dl->edge_stride < p->n_edge))) return VIL_ERR_INVALID_ARGUMENT;
-    if (c->world > 1 && c->has_comm()) return VIL_ERR_UNSUPPORTED;
+    if (c->comm.sharded()) return VIL_ERR_UNSUPPORTED;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(c->device));
     if (producer_stream && (hipStream_t)producer_stream != c->stream) {      // the tables are written by work on another stream: order after it on the device
@@ -2334,7 +1984,7 @@ int vil_marginalize(vil_ctx* c, const vil_problem* p, const vil_state* s, const 
     // under a communicator the collected factors are sharded like a solve's (visual by landmark owner, LiDAR points in slices, the rest on
     // rank 0), A and b are all-reduced ONCE and every rank finishes the small dense part redundantly -- the reference's own pattern
     // (marginalization_factor.cpp:235-264: factors dealt to four threads, private A / b, summed after the join)
-    int st = (c->world > 1 && c->has_comm()) ? upload_sharded(c, &q, s) : upload_impl(c, &q, s, false);
+    int st = (c->comm.sharded()) ? upload_sharded(c, &q, s) : upload_impl(c, &q, s, false);
     if (st != VIL_OK) return st;
     const SolveOpts so = to_dev_opts(o);
     st = init_ctl(c, o, 2);
@@ -2368,28 +2018,18 @@ int vil_shard_ranges(const vil_problem* p, int rank, int world, int32_t* lm_begi
     return VIL_OK;
 }
 
-// bytes this rank sends to EACH peer per trust-region iteration through the library's own exchanges (peer buffers, in-process communicator): the lower
-// triangle of S' + the vectors + its own slice of the landmark arrays.  (RCCL all-reduces the whole set: vil_comm_init.)
 int vil_comm_message_bytes(vil_ctx* c, int64_t* bytes_per_peer, int64_t* bytes_full_set) {
     if (!c || !c->uploaded || !c->split) return VIL_ERR_INVALID_ARGUMENT;
-    const OwnSeg& S = c->own;
-    const size_t D = (size_t)c->D, cam_sent = S.cam - D * (D - 1) / 2;
-    size_t own = 0;
-    if (S.n > 0) own = (size_t)17 * (S.lb[c->rank + 1] - S.lb[c->rank]) + (size_t)6 * (S.fb[c->rank + 1] - S.fb[c->rank]);
-    else own = c->span - S.cam;
-    if (c->slim()) { const SlimLay Y = slim_layout(c); if (bytes_per_peer) *bytes_per_peer = (int64_t)(8 * (Y.camS + Y.gmax)); }      // RCCL: M all-reduced + this rank's padded slice all-gathered
-    else if (c->comm && c->world > 1) { if (bytes_per_peer) *bytes_per_peer = (int64_t)(8 * c->span); }      // RCCL beyond eight ranks: the whole set is all-reduced
-    else if (bytes_per_peer) *bytes_per_peer = (int64_t)(8 * (cam_sent + own));
-    if (bytes_full_set) *bytes_full_set = (int64_t)(8 * c->span);
+    c->comm.message_bytes(c->D, c->span, bytes_per_peer, bytes_full_set);
     return VIL_OK;
 }
 
 // ---- window residency across frames (include/vilsolve.h) ------------------------------------------------------------------------
 int vil_comm_info(vil_ctx* c, int32_t* rank, int32_t* world, int32_t* transport) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    if (rank) *rank = c->rank;
-    if (world) *world = c->world;
-    if (transport) *transport = c->comm ? 1 : (c->lcomm ? 2 : (c->ipc ? (c->ipc->ready ? 3 : -3) : 0));
+    if (rank) *rank = c->comm.rank;
+    if (world) *world = c->comm.world;
+    if (transport) *transport = c->comm.transport();
     return VIL_OK;
 }
 int vil_set_gauge_fix(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->gauge_on = on != 0; return VIL_OK; }      // (takes effect in the next solve)
@@ -2419,9 +2059,10 @@ int vil_lidar_push(vil_ctx* c, int32_t n_plane, const double* plane_const, int32
     if (!c || n_plane < 0 || n_edge < 0 || (n_plane > 0 && !plane_const) || (n_edge > 0 && !edge_const)) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
     const int np_all = n_plane, ne_all = n_edge;
-    if (c->world > 1 && c->has_comm()) {       // factor set sharded over ranks: every rank is handed the whole frame and keeps its contiguous slice
-        const int pb = (int)((long long)n_plane * c->rank / c->world), pe = (int)((long long)n_plane * (c->rank + 1) / c->world);
-        const int eb = (int)((long long)n_edge * c->rank / c->world), ee = (int)((long long)n_edge * (c->rank + 1) / c->world);
+    if (c->comm.sharded()) {       // factor set sharded over ranks: every rank is handed the whole frame and keeps its contiguous slice
+        const int rank = c->comm.rank, world = c->comm.world;
+        const int pb = (int)((long long)n_plane * rank / world), pe = (int)((long long)n_plane * (rank + 1) / world);
+        const int eb = (int)((long long)n_edge * rank / world), ee = (int)((long long)n_edge * (rank + 1) / world);
         plane_const += (size_t)7 * pb; n_plane = pe - pb; edge_const += (size_t)9 * eb; n_edge = ee - eb;
     }
     // capacity: points per slab and number of physical slabs only ever grow (the existing slabs are copied once when they do)
@@ -2526,7 +2167,7 @@ int vil_marginalize_resident(vil_ctx* c, const vil_state* s, const vil_options* 
 // ---- the fully resident window (include/vilsolve.h: vil_win_*; device side: vil_window.hpp) ------------------------------------------
 int vil_win_open(vil_ctx* c, const vil_win_cfg* cfg) {
     if (!c || !cfg || cfg->K < 3 || cfg->K > VIL_WIN_MAXK || cfg->max_tracks < 1 || cfg->max_samples < 1) return VIL_ERR_INVALID_ARGUMENT;
-    if (c->ipc && c->world > 1 && !c->ipc->ready) return VIL_ERR_COMM;
+    if (c->comm.world > 1 && !c->comm.ready()) return VIL_ERR_COMM;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     auto& w = c->win;
@@ -2665,22 +2306,19 @@ int vil_win_solve(vil_ctx* c, const vil_win_problem* wp, vil_state* s, const vil
     // estimator.cpp:1419 / :1487): the device gauge fix is part of the resident window whatever vil_set_gauge_fix was left at
     const bool gauge_was = c->gauge_on; c->gauge_on = true;
     int st;
-    if (c->world > 1 && c->has_comm()) {
+    if (c->comm.sharded()) {
         // SURVEY 8e on the resident window: every rank was handed every frame (vil_win_push_frame: the observation store and the IMU slots are whole on
         // every rank, the LiDAR slabs hold the rank's slice) and is handed the same small tables here; it keeps the visual factors of ITS landmark range
         // -- the rule of vil_shard_ranges on the landmark list -- and rank 0 alone the IMU / prior / ICP / LPS factors.  The prior slot is written by
         // every rank from the all-reduced marginalisation system (identical bits), read by rank 0.
         std::vector<int> lms(L + 1, 0);
         for (int l = 0; l < L; ++l) lms[l + 1] = lms[l] + wp->lm_nobs[l] - 1;
-        OwnSeg& S = c->own; memset(&S, 0, sizeof S);
-        S.n = c->world <= 8 ? c->world : 0; S.Lp = std::max(L, 1);          // (more than eight ranks: RCCL only, which sums the whole set -- n = 0)
-        for (int r = 0; r <= S.n; ++r) { S.lb[r] = shard_cut(lms, L, r, c->world); S.fb[r] = lms[S.lb[r]]; }
-        S.cam = ((size_t)(15 * K + 7) * (15 * K + 7) + 3 * (size_t)(15 * K + 7) + 3 + 1) & ~size_t(1);
-        ws.lb = shard_cut(lms, L, c->rank, c->world); ws.le = shard_cut(lms, L, c->rank + 1, c->world); ws.f0 = lms[ws.lb]; ws.n_vis = lms[ws.le] - lms[ws.lb];
-        c->lm_b = ws.lb; c->lm_e = ws.le;
+        Comm& cm = c->comm;
+        cm.set_owners(lms, L, K);
+        ws.lb = shard_cut(lms, L, cm.rank, cm.world); ws.le = shard_cut(lms, L, cm.rank + 1, cm.world); ws.f0 = lms[ws.lb]; ws.n_vis = lms[ws.le] - lms[ws.lb];
         vil_problem ql = q;
-        if (c->rank != 0) { ql.n_imu = 0; ql.n_icp = 0; ql.n_lps = 0; ql.prior.n = 0; ql.prior.nblk = 0; }
-        st = comm_agree(c, upload_impl(c, &ql, s, true, nullptr, &q, ws.f0, false, &ws));
+        if (cm.rank != 0) { ql.n_imu = 0; ql.n_icp = 0; ql.n_lps = 0; ql.prior.n = 0; ql.prior.nblk = 0; }
+        st = cm.agree(c->stream, upload_impl(c, &ql, s, true, nullptr, &q, ws.f0, false, &ws));
         if (st != VIL_OK) c->uploaded = false;
     } else st = upload_impl(c, &q, s, false, nullptr, nullptr, 0, false, &ws);
     if (st != VIL_OK) { c->gauge_on = gauge_was; return st; }
@@ -2753,84 +2391,32 @@ int vil_win_prior_set(vil_ctx* c, const vil_prior* pr) {
     return VIL_OK;
 }
 
-int vil_comm_unique_id(void* id128) {
-    if (!id128) return VIL_ERR_INVALID_ARGUMENT;
-    if (!g_rccl.load()) return VIL_ERR_COMM;
-    ncclUniqueId id;
-    if (g_rccl.GetUniqueId(&id) != ncclSuccess) return VIL_ERR_COMM;
-    memcpy(id128, id.internal, NCCL_UNIQUE_ID_BYTES);
-    return VIL_OK;
-}
+// ---- multi-GPU set-up (vil_comm.hpp): installing a transport releases whatever the context had, and invalidates the resident problem
+int vil_comm_unique_id(void* id128) { return id128 ? Comm::unique_id(id128) : VIL_ERR_INVALID_ARGUMENT; }
 int vil_comm_init(vil_ctx* c, const void* id128, int rank, int world) {
     if (!c || !id128 || world < 1 || rank < 0 || rank >= world) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    ncclUniqueId id;
-    memcpy(id.internal, id128, NCCL_UNIQUE_ID_BYTES);
-    if (!g_rccl.load()) return VIL_ERR_COMM;
-    if (c->comm) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-    if (g_rccl.CommInitRank(&c->comm, world, id, rank) != ncclSuccess) return VIL_ERR_COMM;
-    c->rank = rank; c->world = world; c->uploaded = false; c->lcomm.reset();
-    return VIL_OK;
+    c->uploaded = false;
+    return c->comm.use_rccl(c->device, id128, rank, world);
 }
-// multi-process peer-buffer exchange: export the inbox, gather the handles (the launcher's job: torch.distributed / MPI / a pipe), import
 int vil_comm_ipc_export(vil_ctx* c, int rank, int world, size_t max_doubles, void* handle64) {
     if (!c || !handle64 || world < 1 || world > 8 || rank < 0 || rank >= world || max_doubles < 64) return VIL_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->ipc) { for (int r = 0; r < c->ipc->world; ++r) if (r != c->ipc->rank && c->ipc->peer_base[r]) hipIpcCloseMemHandle(c->ipc->peer_base[r]); if (c->ipc->base) hipFree(c->ipc->base); c->ipc.reset(); }
-    auto ic = std::make_shared<IpcComm>();
-    ic->world = world; ic->rank = rank; ic->cap = (max_doubles + 31) & ~size_t(31);
-    ic->off_flags = 8 * (size_t)world * 2 * ic->cap; ic->off_seq = ic->off_flags + 64 * (size_t)world * 2;
-    const size_t bytes = ic->off_seq + 256;
-    HIPCHK(hipMalloc((void**)&ic->base, bytes));
-    HIPCHK(hipMemset(ic->base, 0, bytes));
-    hipIpcMemHandle_t h;
-    static_assert(sizeof(hipIpcMemHandle_t) <= 64, "vil_comm_ipc_export hands out 64 bytes");
-    HIPCHK(hipIpcGetMemHandle(&h, ic->base));
-    memset(handle64, 0, 64); memcpy(handle64, &h, sizeof h);
-    ic->peer_base[rank] = ic->base;
-    c->ipc = ic; c->rank = rank; c->world = world; c->uploaded = false; c->lcomm.reset();
-    if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-    return VIL_OK;
+    HIPCHK(hipSetDevice(c->device)); HIPCHK(hipStreamSynchronize(c->stream));
+    c->uploaded = false;
+    return c->comm.export_ipc(c->device, rank, world, max_doubles, handle64);
 }
 int vil_comm_ipc_init(vil_ctx* c, const void* handles) {
-    if (!c || !handles || !c->ipc) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c || !handles) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    IpcComm* ic = c->ipc.get();
-    for (int r = 0; r < ic->world; ++r) {
-        if (r == ic->rank) continue;
-        hipIpcMemHandle_t h; memcpy(&h, (const char*)handles + 64 * (size_t)r, sizeof h);
-        void* p = nullptr;
-        if (hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); return VIL_ERR_COMM; }
-        ic->peer_base[r] = p;
-    }
-    ic->ready = true;
-    return VIL_OK;
+    return c->comm.open_ipc(handles);
 }
-
 int vil_comm_init_local(vil_ctx** ctxs, int n) {
     if (!ctxs || n < 1 || n > 8) return VIL_ERR_INVALID_ARGUMENT;
-    for (int r = 0; r < n; ++r) if (!ctxs[r]) return VIL_ERR_INVALID_ARGUMENT;
-    // k_sum_peers reads the other contexts' buffers directly: contexts on different devices need peer access in both
-    // directions (xGMI / PCIe P2P), checked and enabled here; without it the configuration is refused, not faulted at run time
-    for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) {
-        if (ctxs[a]->device == ctxs[b]->device) continue;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, ctxs[a]->device, ctxs[b]->device) != hipSuccess || !can) return VIL_ERR_UNSUPPORTED;
-        if (hipSetDevice(ctxs[a]->device) != hipSuccess) return VIL_ERR_DEVICE;
-        const hipError_t e = hipDeviceEnablePeerAccess(ctxs[b]->device, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return VIL_ERR_UNSUPPORTED;
-        (void)hipGetLastError();
-    }
-    auto lc = std::make_shared<LocalComm>();
-    if (pthread_barrier_init(&lc->bar, nullptr, (unsigned)n) != 0) return VIL_ERR_COMM;
-    lc->n = n;
-    for (int r = 0; r < n; ++r) {
-        vil_ctx* c = ctxs[r];
-        if (c->comm) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-        c->lcomm = lc; c->rank = r; c->world = n; c->uploaded = false; c->ipc.reset();
-    }
-    return VIL_OK;
+    Comm* ranks[8]; int devices[8];
+    for (int r = 0; r < n; ++r) { if (!ctxs[r]) return VIL_ERR_INVALID_ARGUMENT; ranks[r] = &ctxs[r]->comm; devices[r] = ctxs[r]->device; }
+    const int st = Comm::join_local(ranks, devices, n);
+    if (st == VIL_OK) for (int r = 0; r < n; ++r) ctxs[r]->uploaded = false;
+    return st;
 }
 
 // ---- the lab bench (include/vilsolve_debug.h): test hooks and the profilers of the kernels' role layout ------------------------------------------
@@ -2849,7 +2435,7 @@ int vil_debug_drop_flag(vil_ctx* c, int32_t role, int32_t launch) {
     return VIL_OK;
 }
 int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
-int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->slim_emul = on != 0; return VIL_OK; }
+int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->comm.slim_emul = on != 0; return VIL_OK; }
 int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) {
     if (!c || !A || !L || !x || !ok || D < 1 || D > 159 || variant < 0 || variant > 1) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));

@@ -247,6 +247,54 @@ print("WINDOW_SHARD_OK")
 '''
 
 
+REPLACE_SCRIPT = r'''
+import sys, os, ctypes as C, threading
+sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests"))
+import numpy as np
+import __graft_entry__ as g; g.load_package()
+from mvil_fusion_amd import abi, lib, synth
+def info(b):
+    v = [C.c_int32(-9) for _ in range(3)]
+    assert b.lib.vil_comm_info(b.ctx, *[C.byref(x) for x in v]) == 0
+    return tuple(x.value for x in v)
+def pair(export_first):
+    """one 2-rank sharded solve of configuration 1 through the in-process communicator; export_first: both contexts carried an exported,
+    never opened peer-buffer communicator before they were joined"""
+    bes = [lib.open_vilsolve() for _ in range(2)]
+    if export_first:
+        f = bes[0].lib.vil_comm_ipc_export; f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+        for r, b in enumerate(bes):
+            assert f(b.ctx, r, 2, 400000, (C.c_char * 64)()) == 0
+            assert info(b) == (r, 2, -3), info(b)
+    assert bes[0].lib.vil_comm_init_local((C.c_void_p * 2)(*[b.ctx for b in bes]), 2) == 0
+    for r, b in enumerate(bes): assert info(b) == (r, 2, 2), info(b)           # ONE transport: the in-process one
+    ws = [synth.make_config(1) for _ in range(2)]
+    res = [None] * 2
+    def run(r):
+        try: res[r] = ("ok", bes[r].solve(ws[r]))
+        except Exception as e: res[r] = ("err", repr(e))
+    th = [threading.Thread(target=run, args=(r,)) for r in range(2)]
+    [t.start() for t in th]; [t.join(300) for t in th]
+    assert all(x is not None and x[0] == "ok" for x in res), res
+    for b in bes: b.close()
+    return [(res[r][1].iterations, np.float64(res[r][1].final_cost), ws[r].pose, ws[r].speedbias, ws[r].inv_depth, ws[r].ex_pose) for r in range(2)]
+fresh, replaced = pair(False), pair(True)
+assert fresh[0][0] > 1
+for r in range(2):
+    for a, b in zip(fresh[r], replaced[r]): assert np.array_equal(a, b), (r, a, b)
+    for a, b in zip(replaced[r], replaced[0]): assert np.array_equal(a, b), (r, a, b)
+print("REPLACE_OK")
+'''
+
+
+def test_replacing_an_exported_peer_buffer_communicator_leaves_a_working_context():
+    """Two contexts on one device export a peer-buffer communicator (world 2) that is never opened, then join the in-process communicator: vil_comm_info
+    reports the in-process transport on both, and the sharded solve returns on both ranks the bits of the same solve on two contexts that never exported."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")      # (as tests/test_gpu_ipc.py exports its inboxes)
+    out = subprocess.run([sys.executable, "-c", REPLACE_SCRIPT % (ROOT, ROOT)], env=env, capture_output=True, text=True, timeout=600)
+    assert "REPLACE_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
 def test_resident_window_under_a_communicator():
     """vil_win_* on 2 and 3 ranks (in-process communicator, one device): every rank is handed every frame (whole observation store and IMU slots, ITS
     slice of each LiDAR slab) and the same landmark list, keeps the visual factors of its landmark range, and writes the SAME new prior into its own device
