@@ -19,6 +19,7 @@
 #include "../../include/vilsolve_debug.h"
 #include "vil_internal.h"
 #include "vil_comm.hpp"
+#include "vil_resident.hpp"
 #include "vil_tuning.hpp"
 #include "vil_coop.hpp"
 #include "vil_dev.hpp"
@@ -84,6 +85,7 @@ struct vil_ctx {
     bool uploaded = false;
     int resident_kind = 0;         // 1: a window handed over through vil_upload / vil_solve (the only kind vil_solve_resident accepts);
                                    // 2: a derived problem of vil_marginalize / vil_eval_factors / vil_linearize (they replace the resident window)
+    void invalidate() { uploaded = false; resident_kind = 0; }      // nothing is resident: the next solve needs an upload
     int K = 0, L = 0, D = 0, NS = 0;
     size_t off_x0 = 0;             // backup of the uploaded state (device)
     double* d_x0 = nullptr;
@@ -130,13 +132,7 @@ struct vil_ctx {
     int last_live = 5;             // live sweep launches of the previous solve (sizes the first launch chunk)
     int recent_live[8] = {5, 5, 5, 5, 5, 5, 5, 5}; int recent_at = 0;      // ... of the last eight solves: the first solve of an upload (a tracker's image) is sized by their maximum
     // ---- window residency across frames (vil_lidar_*, vil_set_gauge_fix, vil_marginalize_resident) --------------------------------
-    struct Slab { int np, ne, slot; int np_all, ne_all; };      // np_all / ne_all: the frame's points BEFORE a communicator's slicing (the same on every rank)
-    std::vector<Slab> slabs;       // window order: slab i <-> pose K - count + i
-    std::vector<int> free_slots;
-    int cap_p = 0, cap_e = 0, nslot = 0;      // points per slab (capacity), physical slabs
-    double* d_pl = nullptr; double* d_ed = nullptr;       // component-major: row q of the plane table at d_pl + q * nslot * cap_p
-    double* d_lstage = nullptr; double* h_lstage = nullptr; size_t lstage_cap = 0;     // AoS staging of one pushed frame (device / pinned)
-    hipEvent_t lpush_ev = nullptr; bool lpush_pending = false;
+    LidarSlabs lidar;              // LiDAR frame slabs (vil_resident.hpp)
     bool lidar_resident = false;   // the resident problem takes its point factors from the slabs
     bool gauge_on = false;
     struct MargMeta {              // what vil_marginalize_resident needs to know about the resident window (captured at upload)
@@ -145,28 +141,7 @@ struct vil_ctx {
         int n_lm0 = 0; bool imu01 = false; bool lidar0 = false; bool use_td = false;
         std::vector<int> icp_ids, lps_ids;
     } mm;
-    // ---- the fully resident window (vil_win_*, vil_window.hpp) ---------------------------------------------------------------------
-    struct WinStore {
-        bool open = false; vil_win_cfg cfg;
-        int K = 0, T = 0, S = 0, NF = 0, nmax = 0, x0max = 0;
-        std::vector<int> fslot, islot, free_f, free_i;           // window frame -> observation slot / IMU slot; free lists
-        std::vector<int> ns; std::vector<double> sum_dt;          // per IMU slot: samples held, duration of the interval
-        double* d_store = nullptr; double* d_samp = nullptr; double* d_hdr = nullptr; double* d_rec = nullptr; double* d_U = nullptr;
-        double* d_prior[2] = {nullptr, nullptr}; int cur = 0;     // prior slots: [J0 nmax^2 | r0 nmax | x0 x0max | pH nmax^2 | pg0 nmax | pc0 8]
-        int pn = 0, pm = 0; std::vector<int> pkind, pindex, pcol;  // the current prior's block structure (host)
-        int* d_wstat = nullptr;                                   // sticky status of the asynchronous work (a covariance that is not positive definite, a prior that is not finite)
-        char* h_stage = nullptr; char* d_stage = nullptr; size_t stage_cap = 0; hipEvent_t ev = nullptr; bool pending = false;
-        double* dt(int q) const { return d_samp + (size_t)q * 7 * S; }
-        double* acc(int q) const { return dt(q) + S; }
-        double* gyr(int q) const { return dt(q) + 4 * (size_t)S; }
-        double* pJ0(int w) const { return d_prior[w]; }
-        double* pr0(int w) const { return d_prior[w] + (size_t)nmax * nmax; }
-        double* px0(int w) const { return pr0(w) + nmax; }
-        double* pH(int w) const { return px0(w) + x0max; }
-        double* pg0(int w) const { return pH(w) + (size_t)nmax * nmax; }
-        double* pc0(int w) const { return pg0(w) + nmax; }
-        size_t prior_doubles() const { return 2 * (size_t)nmax * nmax + 2 * (size_t)nmax + x0max + 8; }
-    } win;
+    Window win;                    // the fully resident window (vil_win_*: vil_resident.hpp, vil_window.hpp)
     bool profiling = false, stamps = false; long long period_n = 0;
     std::vector<unsigned long long> last_stamps;      // raw stamps of the last profiled solve (vil_debug_read_stamps)
     int wg_launch = -1;      // (vil_profile_workgroups)
@@ -257,10 +232,6 @@ __global__ __launch_bounds__(VIL_STEP_THREADS) void k_debug_dense(const double* 
     for (int e = t; e < D; e += blockDim.x) xout[e] = ok ? s.y[e] : 0.0;
     if (t == 0) okout[0] = ok ? 1 : 0;
 }
-__global__ void k_aos2soa(const double* aos, int n, int ncomp, double* dst, size_t stride) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < n) for (int q = 0; q < ncomp; ++q) dst[(size_t)q * stride + f] = aos[(size_t)f * ncomp + q];
-}
 extern "C" {
 
 int vil_abi_version(void) { return VIL_ABI_VERSION; }
@@ -337,13 +308,8 @@ void vil_destroy(vil_ctx* c) {
     if (c->d_imu_perm) hipFree(c->d_imu_perm);
     for (auto& ct : c->chtabs) { if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h); if (ct.ev) hipEventDestroy(ct.ev); }
     if (c->d_prof) hipFree(c->d_prof);
-    if (c->d_pl) hipFree(c->d_pl);
-    if (c->d_ed) hipFree(c->d_ed);
-    if (c->d_lstage) hipFree(c->d_lstage);
-    if (c->h_lstage) hipHostFree(c->h_lstage);
-    if (c->lpush_ev) hipEventDestroy(c->lpush_ev);
-    { auto& w = c->win; hipFree(w.d_store); hipFree(w.d_samp); hipFree(w.d_hdr); hipFree(w.d_rec); hipFree(w.d_U); hipFree(w.d_prior[0]); hipFree(w.d_prior[1]); hipFree(w.d_wstat); hipFree(w.d_stage);
-      if (w.h_stage) hipHostFree(w.h_stage); if (w.ev) hipEventDestroy(w.ev); }
+    c->lidar.release();
+    c->win.release();
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -385,8 +351,7 @@ static int validate(const vil_problem* p, const vil_state* s, bool device_lidar 
             const int kind = pr.blk_kind[b], idx = pr.blk_index[b];
             if (kind < VIL_BLK_POSE || kind > VIL_BLK_TD) return VIL_ERR_INVALID_ARGUMENT;
             if ((kind == VIL_BLK_POSE || kind == VIL_BLK_SPEEDBIAS) && (idx < 0 || idx >= p->K)) return VIL_ERR_INVALID_ARGUMENT;
-            const int ls = (kind == VIL_BLK_POSE || kind == VIL_BLK_EX) ? 6 : (kind == VIL_BLK_SPEEDBIAS ? 9 : 1);
-            if (pr.blk_col[b] < 0 || pr.blk_col[b] + ls > pr.n) return VIL_ERR_INVALID_ARGUMENT;
+            if (pr.blk_col[b] < 0 || pr.blk_col[b] + blk_cols(kind) > pr.n) return VIL_ERR_INVALID_ARGUMENT;
         }
     }
     return VIL_OK;
@@ -550,15 +515,12 @@ int vil_visual_plan(const vil_problem* p, vil_visual_plan_info* info, int32_t ma
 
 
 // gp / vis_f0 (sharded): the whole window's problem and the index of this rank's first visual factor in it
-// Resident sources of the big tables (vil_win_solve, vil_window.hpp): the visual factor tables are expanded on the device from the landmark
-// list + observation store, IMU records / sqrt-information come from the IMU slots, the prior is the device prior slot.  The vil_problem
-// handed to upload_impl then carries n_vis = 0, imu_const = NULL and the prior's block tables only.
-struct WinSrc {
+// Resident sources of the big tables (vil_win_solve): the visual factor tables are expanded on the device from the landmark
+// list + observation store, IMU records / sqrt-information come from the IMU slots, the prior is the device prior slot (WinSlots: what Window::fill
+// sets).  The vil_problem handed to upload_impl then carries n_vis = 0, imu_const = NULL and the prior's block tables only.
+struct WinSrc : WinSlots {
     const int* lm_track; const int* lm_startf; const int* lm_nobs;      // host, L each
-    int n_vis, T;
-    const double* d_store; const int* fslot; const int* islot;          // slots of the window frames (host, K each)
-    const double* d_rec; const double* d_U; const double* sum_dt;       // IMU slots (device) and the intervals' durations (host, per physical slot)
-    const double* pJ0; const double* pr0; const double* px0; double* pH; double* pg0; double* pc0;     // device prior slot (prior.n > 0)
+    int n_vis;
     int lb, le, f0, n_vis_all;       // sharded (gp != null): this rank keeps the factors of landmarks [lb, le), the first of which is factor f0 of the n_vis_all of the window
 };
 
@@ -615,7 +577,7 @@ static int upload_visual(vil_ctx* c, ImageBuilder& im, const vil_problem* p, con
     } else landmark_frames(p, lms, fmin, fmax, anch);
     VisPlan vp;
     int npt = std::max(p->n_plane, 0), net = std::max(p->n_edge, 0);           // LiDAR points of this upload (resident slabs: what they hold)
-    if (p->n_plane == VIL_LIDAR_RESIDENT) for (auto& sl : c->slabs) { npt += sl.np; net += sl.ne; }
+    if (p->n_plane == VIL_LIDAR_RESIDENT) c->lidar.totals(&npt, &net);
     int vwg_max = visual_wg_budget(p->n_imu, npt, net), cap_forced = 0;
     if (const char* ev = VIL_TUNE_ENV("VIL_VWG")) vwg_max = std::max(1, atoi(ev));
     if (const char* ev = VIL_TUNE_ENV("VIL_VCAP")) cap_forced = std::max(1, atoi(ev));
@@ -689,12 +651,10 @@ static int upload_lidar(vil_ctx* c, ImageBuilder& im, const vil_problem* p, cons
     // one kind of point factor (plane: 7 components, edge: 9): its chunk list, and for the caller's points the pose-sorted SoA table.  Only the chunk list for
     // device-resident tables (vil_internal.h: every factor sits on pose 0 in the caller's order) and resident frame slabs (vil_lidar_push: slab i belongs to pose K - count + i)
     auto kind = [&](bool plane, int n, const int* pose, const double* cst, std::vector<int>& perm, const double** soa, int* stride, int* nchunk, const int** tab, int base) {
-        const int ns = (int)c->slabs.size(), ncomp = plane ? 7 : 9;
+        const int ncomp = plane ? 7 : 9;
         ch.clear(); perm.clear();
-        if (res_lidar) for (int i = 0; i < ns; ++i) {
-            const int m = plane ? c->slabs[i].np : c->slabs[i].ne, cap = plane ? c->cap_p : c->cap_e;
-            for (int s0 = 0; s0 < m; s0 += VIL_THREADS) { ch.push_back(c->slabs[i].slot * cap + s0); ch.push_back(std::min(VIL_THREADS, m - s0)); ch.push_back(K - ns + i); }
-        } else if (dl) for (int s0 = 0; s0 < n; s0 += VIL_THREADS) { ch.push_back(s0); ch.push_back(std::min(VIL_THREADS, n - s0)); ch.push_back(0); }
+        if (res_lidar) c->lidar.chunks(plane, K, ch);
+        else if (dl) for (int s0 = 0; s0 < n; s0 += VIL_THREADS) { ch.push_back(s0); ch.push_back(std::min(VIL_THREADS, n - s0)); ch.push_back(0); }
         if (res_lidar || dl) im.put(nullptr, 8, (void**)soa);
         else {
             lidar_order(n, pose, K, perm, cnt); lidar_chunks(cnt, K, ch);
@@ -706,15 +666,15 @@ static int upload_lidar(vil_ctx* c, ImageBuilder& im, const vil_problem* p, cons
         for (int k = 0; k < K; ++k) lcp[base + k + 1] += lcp[base + k];
         im.put(ch.data(), 4 * ch.size(), (void**)tab);
     };
-    if (res_lidar && (int)c->slabs.size() > K) return VIL_ERR_UNSUPPORTED;
+    if (res_lidar && c->lidar.count() > K) return VIL_ERR_UNSUPPORTED;
     c->mm.lidar0 = false;
     kind(true, p->n_plane, p->plane_pose, p->plane_const, c->plane_perm, &P.pl_c, &P.pl_stride, &P.n_pchunk, &P.pchunk, 0);
     kind(false, p->n_edge, p->edge_pose, p->edge_const, c->edge_perm, &P.ed_c, &P.ed_stride, &P.n_echunk, &P.echunk, K + 1);
     P.n_plane = p->n_plane; P.n_edge = p->n_edge;
-    if (res_lidar) { P.n_plane = P.n_edge = 0; for (auto& sl : c->slabs) { P.n_plane += sl.np; P.n_edge += sl.ne; } }
+    if (res_lidar) c->lidar.totals(&P.n_plane, &P.n_edge);
     // (resident slabs under a communicator: a frame with fewer points than ranks leaves some ranks' slices empty -- whether pose 0 carries LiDAR factors, and with it the
     //  kept / dropped layout of the marginalisation every rank commits, is decided from the UNSLICED counts)
-    if (res_lidar) c->mm.lidar0 = (int)c->slabs.size() == K && c->slabs[0].np_all + c->slabs[0].ne_all > 0;
+    if (res_lidar) c->mm.lidar0 = c->lidar.frame0_has_points(K);
     im.put(nullptr, 8 * (size_t)28 * std::max(P.n_pchunk + P.n_echunk, 1), (void**)&P.lpart);
     im.put(lcp.data(), 4 * lcp.size(), (void**)&P.lchunk_pose);
     return VIL_OK;
@@ -747,7 +707,7 @@ static int upload_imu_prior(vil_ctx* c, ImageBuilder& im, const vil_problem* p, 
         std::vector<int> xoff(pr.nblk), pmap(n, -1);
         int xo = 0, jo = 0;
         for (int b = 0; b < pr.nblk; ++b) {
-            const int kind = pr.blk_kind[b], gs = (kind == VIL_BLK_POSE || kind == VIL_BLK_EX) ? 7 : (kind == VIL_BLK_SPEEDBIAS ? 9 : 1), ls = gs == 7 ? 6 : gs;
+            const int kind = pr.blk_kind[b], gs = blk_doubles(kind), ls = blk_cols(kind);
             xoff[b] = xo; xo += gs; c->prior_joff.push_back(jo); jo += n * gs;
             int col = -1;
             const int idx = pr.blk_index[b];
@@ -906,7 +866,7 @@ static int commit(vil_ctx* c, ImageBuilder& im, DevP& P, bool pre_ok, const vil_
     if (dl) { P.pl_c = dl->plane_soa; P.pl_stride = dl->plane_stride; P.ed_c = dl->edge_soa; P.ed_stride = dl->edge_stride; }
     if (!gp) { P.glm_start = P.lm_start; P.glm_acol = P.lm_acol; P.gfcol = P.fcol; }
     if (pre_ok) { const vil_ctx::ChTab& ct = c->chtabs[c->chtab_cur]; P.chtab = ct.d; P.chpq = ct.d + 4 * (size_t)ct.n; }
-    if (c->lidar_resident) { P.pl_c = c->d_pl; P.pl_stride = c->nslot * c->cap_p; P.ed_c = c->d_ed; P.ed_stride = c->nslot * c->cap_e; }
+    if (c->lidar_resident) c->lidar.tables(P);
     if (ws && P.pn) { P.px0 = ws->px0; P.pJ0 = ws->pJ0; P.pr0 = ws->pr0; P.pH = ws->pH; P.pg0 = ws->pg0; P.pc0 = ws->pc0; }      // the device prior slot, contractions included
     const size_t Lp = (size_t)std::max(P.L, 1), D = P.D;
     for (int q = 0; q < 2; ++q) {
@@ -1072,7 +1032,7 @@ static int upload_setup(vil_ctx* c, const WinSrc* ws, bool check_setup, const in
         // would compute (sqrt-information, prior contractions) already sits next to its source
         WinPack W; memset(&W, 0, sizeof W);
         W.L = P.L; W.F = P.n_vis; W.stride = P.vis_stride; W.T = ws->T;
-        W.lm_start = P.lm_start; W.lm_track = wd_track; W.lm_startf = wd_startf; W.store = ws->d_store;
+        W.lm_start = P.lm_start; W.lm_track = wd_track; W.lm_startf = wd_startf; W.store = ws->store;
         for (int k = 0; k < P.K; ++k) { W.fslot[k] = ws->fslot[k]; W.islot[k] = ws->islot[k]; }
         W.vis_c = const_cast<double*>(P.vis_c); W.vis_i = const_cast<int*>(P.vis_i); W.vis_j = const_cast<int*>(P.vis_j); W.vis_l = const_cast<int*>(P.vis_l); W.fcol = const_cast<int*>(P.fcol); W.vfinv = P.vfinv;
         W.n_imu = P.n_imu; W.rec = ws->d_rec; W.U = ws->d_U; W.imu_c = const_cast<double*>(P.imu_c); W.imu_U = const_cast<double*>(P.imu_U);
@@ -1098,8 +1058,8 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     int st = validate(p, s, dl != nullptr, ws != nullptr);
     if (st != VIL_OK) return st;                 // an invalid problem leaves the resident one untouched
-    c->uploaded = false;                         // from here on the arena is rewritten: resident only again after a complete upload
-    c->resident_kind = 0; c->reset_pending = false;
+    c->invalidate();                             // from here on the arena is rewritten: resident only again after a complete upload
+    c->reset_pending = false;
     HIPCHK(hipSetDevice(c->device));
 #ifdef VIL_TUNING
     static const bool up_trace = getenv("VIL_UPLOAD_TRACE") != nullptr;
@@ -1706,7 +1666,7 @@ int vil_eval_factors(vil_ctx* c, const vil_problem* p, const vil_state* s, int c
         case VIL_FACTOR_LPS: nfac = P.n_lps; nr = 3; nj = 42; break;
         case VIL_FACTOR_EDGE: nfac = P.n_edge; nr = 3; nj = 21; break;
         case VIL_FACTOR_PLANE: nfac = P.n_plane; nr = 1; nj = 7; break;
-        case VIL_FACTOR_PRIOR: nfac = P.pn ? 1 : 0; nr = P.pn; nj = 0; for (int b = 0; b < P.pnblk; ++b) { int k = p->prior.blk_kind[b]; nj += (size_t)P.pn * ((k == 0 || k == 2) ? 7 : (k == 1 ? 9 : 1)); } break;
+        case VIL_FACTOR_PRIOR: nfac = P.pn ? 1 : 0; nr = P.pn; nj = 0; for (int b = 0; b < P.pnblk; ++b) nj += (size_t)P.pn * blk_doubles(p->prior.blk_kind[b]); break;
         default: return VIL_ERR_INVALID_ARGUMENT;
     }
     if (nfac == 0) return VIL_OK;
@@ -1863,31 +1823,12 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
     if (to_slot) {
         // resident window: the new prior goes device-to-device into the other prior slot (J0, r0, x0 from the device state, contractions);
         // nothing is read back, nothing is waited for.  A non-finite result raises the window's status word.
-        auto& w = c->win;
-        if (n > w.nmax || (int)kinds.size() > VIL_WIN_MAXBLK) return VIL_ERR_UNSUPPORTED;
-        const int dst = 1 - w.cur;
-        PriorCommit pc; memset(&pc, 0, sizeof pc);
-        pc.n = n; pc.nblk = (int)kinds.size(); pc.J0 = M.J0; pc.r0 = M.r0; pc.x = c->P.x[0]; pc.K = K;
-        for (size_t b = 0; b < kinds.size(); ++b) { pc.kind[b] = kinds[b]; pc.index[b] = index[b]; }
-        pc.pJ0 = w.pJ0(dst); pc.pr0 = w.pr0(dst); pc.px0 = w.px0(dst); pc.pH = w.pH(dst); pc.pg0 = w.pg0(dst); pc.pc0 = w.pc0(dst); pc.status = w.d_wstat;
-        {
-            const size_t pl = 8 * ((size_t)n * (n + 1) + n + 8);
-            if (pl > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_prior_commit, pl));
-            hipLaunchKernelGGL(k_prior_commit, dim3(16), dim3(256), pl, c->stream, pc);
-        }
-        w.cur = dst; w.pn = n; w.pm = nd + n_lm_elim;
-        w.pkind.assign(kinds.begin(), kinds.end()); w.pindex.clear(); w.pcol.clear();
-        int col = 0;
-        for (size_t b = 0; b < kinds.size(); ++b) {
-            const int kind = kinds[b], idx = index[b];
-            int ni = idx;
-            if (kind == VIL_BLK_POSE || kind == VIL_BLK_SPEEDBIAS) ni = old_ ? idx - 1 : (idx == K - 1 ? K - 2 : idx);      // the address shift as an index remap (estimator.cpp:1599-1611, 1654-1677)
-            w.pindex.push_back(ni); w.pcol.push_back(col);
-            col += (kind == VIL_BLK_POSE || kind == VIL_BLK_EX) ? 6 : (kind == VIL_BLK_SPEEDBIAS ? 9 : 1);
-        }
+        st = c->win.commit_prior(c->stream, K, old_, n, nd + n_lm_elim, (int)kinds.size(), kinds.data(), index.data(), nullptr, M.J0, M.r0, c->P.x[0]);
+        if (st != VIL_OK) return st;
         if (winfo) {
-            winfo->n = n; winfo->nblk = (int)kinds.size(); winfo->m = w.pm;
-            for (size_t b = 0; b < kinds.size(); ++b) { winfo->blk_kind[b] = w.pkind[b]; winfo->blk_index[b] = w.pindex[b]; winfo->blk_col[b] = w.pcol[b]; }
+            vil_prior pb; c->win.prior_blocks(pb);
+            winfo->n = n; winfo->nblk = pb.nblk; winfo->m = nd + n_lm_elim;
+            for (int b = 0; b < pb.nblk; ++b) { winfo->blk_kind[b] = pb.blk_kind[b]; winfo->blk_index[b] = pb.blk_index[b]; winfo->blk_col[b] = pb.blk_col[b]; }
         }
         return VIL_OK;
     }
@@ -1912,11 +1853,9 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
     for (size_t b = 0; b < kinds.size(); ++b) {
         const int kind = kinds[b], idx = index[b];
         out->blk_kind[b] = kind;
-        int ni = idx;
-        if (kind == VIL_BLK_POSE || kind == VIL_BLK_SPEEDBIAS) ni = old_ ? idx - 1 : (idx == K - 1 ? K - 2 : idx);
-        out->blk_index[b] = ni; out->blk_col[b] = col;
+        out->blk_index[b] = blk_shift(kind, idx, old_, K); out->blk_col[b] = col;
         const double* src = kind == VIL_BLK_POSE ? hx + 7 * idx : (kind == VIL_BLK_SPEEDBIAS ? hx + 7 * K + 9 * idx : (kind == VIL_BLK_EX ? hx + 16 * K : hx + 16 * K + 7));
-        const int gs = (kind == VIL_BLK_POSE || kind == VIL_BLK_EX) ? 7 : (kind == VIL_BLK_SPEEDBIAS ? 9 : 1), ls = gs == 7 ? 6 : gs;
+        const int gs = blk_doubles(kind), ls = blk_cols(kind);
         for (int k = 0; k < gs; ++k) out->x0[xo + k] = src[k];
         xo += gs; col += ls;
     }
@@ -2036,77 +1975,32 @@ int vil_set_gauge_fix(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_A
 
 int vil_lidar_reset(vil_ctx* c) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    c->slabs.clear(); c->free_slots.clear();
-    for (int q = c->nslot - 1; q >= 0; --q) c->free_slots.push_back(q);
-    if (c->lidar_resident) { c->uploaded = false; c->resident_kind = 0; }      // the resident window's chunk list points into the old slab order
+    c->lidar.reset();
+    if (c->lidar_resident) c->invalidate();      // the resident window's chunk list points into the old slab order
     return VIL_OK;
 }
 int vil_lidar_count(vil_ctx* c, int32_t* n_slabs, int32_t* n_plane, int32_t* n_edge) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     int np = 0, ne = 0;
-    for (auto& sl : c->slabs) { np += sl.np; ne += sl.ne; }
-    if (n_slabs) *n_slabs = (int)c->slabs.size(); if (n_plane) *n_plane = np; if (n_edge) *n_edge = ne;
+    c->lidar.totals(&np, &ne);
+    if (n_slabs) *n_slabs = c->lidar.count(); if (n_plane) *n_plane = np; if (n_edge) *n_edge = ne;
     return VIL_OK;
 }
 int vil_lidar_drop(vil_ctx* c, int32_t slab) {
-    if (!c || slab < 0 || slab >= (int)c->slabs.size()) return VIL_ERR_INVALID_ARGUMENT;
-    c->free_slots.push_back(c->slabs[slab].slot);
-    c->slabs.erase(c->slabs.begin() + slab);          // the later frames move down: an index remap, the points stay where they are
-    if (c->lidar_resident) { c->uploaded = false; c->resident_kind = 0; }      // slab <-> pose changed under the resident window's chunk list
+    if (!c || slab < 0 || slab >= c->lidar.count()) return VIL_ERR_INVALID_ARGUMENT;
+    c->lidar.drop(slab);
+    if (c->lidar_resident) c->invalidate();      // slab <-> pose changed under the resident window's chunk list
     return VIL_OK;
 }
 int vil_lidar_push(vil_ctx* c, int32_t n_plane, const double* plane_const, int32_t n_edge, const double* edge_const) {
     if (!c || n_plane < 0 || n_edge < 0 || (n_plane > 0 && !plane_const) || (n_edge > 0 && !edge_const)) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    const int np_all = n_plane, ne_all = n_edge;
-    if (c->comm.sharded()) {       // factor set sharded over ranks: every rank is handed the whole frame and keeps its contiguous slice
-        const int rank = c->comm.rank, world = c->comm.world;
-        const int pb = (int)((long long)n_plane * rank / world), pe = (int)((long long)n_plane * (rank + 1) / world);
-        const int eb = (int)((long long)n_edge * rank / world), ee = (int)((long long)n_edge * (rank + 1) / world);
-        plane_const += (size_t)7 * pb; n_plane = pe - pb; edge_const += (size_t)9 * eb; n_edge = ee - eb;
-    }
-    // capacity: points per slab and number of physical slabs only ever grow (the existing slabs are copied once when they do)
-    if (n_plane > c->cap_p || n_edge > c->cap_e || c->free_slots.empty()) {
-        const int ncp = std::max(c->cap_p, ((n_plane + n_plane / 4 + 255) / 256) * 256), nce = std::max(c->cap_e, ((n_edge + n_edge / 4 + 255) / 256) * 256);
-        const int nns = std::max(c->nslot, (int)c->slabs.size() + 4);
-        double *npl = nullptr, *ned = nullptr;
-        HIPCHK(hipMalloc(&npl, 8 * (size_t)7 * nns * std::max(ncp, 256))); HIPCHK(hipMalloc(&ned, 8 * (size_t)9 * nns * std::max(nce, 256)));
-        const int cp2 = std::max(ncp, 256), ce2 = std::max(nce, 256);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (auto& sl : c->slabs) {
-            for (int q = 0; q < 7 && sl.np; ++q) HIPCHK(hipMemcpyAsync(npl + ((size_t)q * nns + sl.slot) * cp2, c->d_pl + ((size_t)q * c->nslot + sl.slot) * c->cap_p, 8 * (size_t)sl.np, hipMemcpyDeviceToDevice, c->stream));
-            for (int q = 0; q < 9 && sl.ne; ++q) HIPCHK(hipMemcpyAsync(ned + ((size_t)q * nns + sl.slot) * ce2, c->d_ed + ((size_t)q * c->nslot + sl.slot) * c->cap_e, 8 * (size_t)sl.ne, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_pl) hipFree(c->d_pl); if (c->d_ed) hipFree(c->d_ed);
-        c->d_pl = npl; c->d_ed = ned;
-        for (int q = nns - 1; q >= c->nslot; --q) c->free_slots.push_back(q);
-        c->cap_p = cp2; c->cap_e = ce2; c->nslot = nns;
-        c->uploaded = false;                          // a resident problem holds pointers / strides of the old tables
-    }
-    const size_t need = (size_t)7 * n_plane + (size_t)9 * n_edge;
-    if (need > c->lstage_cap) {
-        if (c->lpush_pending) { HIPCHK(hipEventSynchronize(c->lpush_ev)); c->lpush_pending = false; }
-        if (c->d_lstage) hipFree(c->d_lstage); if (c->h_lstage) hipHostFree(c->h_lstage);
-        c->d_lstage = nullptr; c->h_lstage = nullptr; c->lstage_cap = 0;
-        const size_t cap = need + need / 4 + 1024;
-        HIPCHK(hipMalloc(&c->d_lstage, 8 * cap)); HIPCHK(hipHostMalloc(&c->h_lstage, 8 * cap, hipHostMallocDefault));
-        c->lstage_cap = cap;
-    }
-    if (c->lpush_pending) { HIPCHK(hipEventSynchronize(c->lpush_ev)); c->lpush_pending = false; }     // the previous frame's DMA has left the pinned image
-    const int slot = c->free_slots.back(); c->free_slots.pop_back();
-    if (need) {
-        if (n_plane) memcpy(c->h_lstage, plane_const, 8 * (size_t)7 * n_plane);
-        if (n_edge) memcpy(c->h_lstage + (size_t)7 * n_plane, edge_const, 8 * (size_t)9 * n_edge);
-        HIPCHK(hipMemcpyAsync(c->d_lstage, c->h_lstage, 8 * need, hipMemcpyHostToDevice, c->stream));
-        if (!c->lpush_ev) HIPCHK(hipEventCreateWithFlags(&c->lpush_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->lpush_ev, c->stream)); c->lpush_pending = true;
-        // point-major rows -> the component-major tables the sweep reads (coalesced, thread = point)
-        if (n_plane) hipLaunchKernelGGL(k_aos2soa, dim3((n_plane + 255) / 256), dim3(256), 0, c->stream, c->d_lstage, n_plane, 7, c->d_pl + (size_t)slot * c->cap_p, (size_t)c->nslot * c->cap_p);
-        if (n_edge) hipLaunchKernelGGL(k_aos2soa, dim3((n_edge + 255) / 256), dim3(256), 0, c->stream, c->d_lstage + (size_t)7 * n_plane, n_edge, 9, c->d_ed + (size_t)slot * c->cap_e, (size_t)c->nslot * c->cap_e);
-    }
-    c->slabs.push_back({n_plane, n_edge, slot, np_all, ne_all});
-    if (c->lidar_resident) { c->uploaded = false; c->resident_kind = 0; }      // (a recycled slot would feed this frame's points to the old pose)
+    const bool sh = c->comm.sharded();
+    bool tables_moved = false;
+    const int st = c->lidar.push(c->stream, sh ? c->comm.rank : 0, sh ? c->comm.world : 1, n_plane, plane_const, n_edge, edge_const, &tables_moved);
+    if (tables_moved) c->uploaded = false;       // a resident problem holds pointers / strides of the old tables
+    if (st != VIL_OK) return st;
+    if (c->lidar_resident) c->invalidate();      // (a recycled slot would feed this frame's points to the old pose)
     return VIL_OK;
 }
 
@@ -2169,116 +2063,45 @@ int vil_win_open(vil_ctx* c, const vil_win_cfg* cfg) {
     if (!c || !cfg || cfg->K < 3 || cfg->K > VIL_WIN_MAXK || cfg->max_tracks < 1 || cfg->max_samples < 1) return VIL_ERR_INVALID_ARGUMENT;
     if (c->comm.world > 1 && !c->comm.ready()) return VIL_ERR_COMM;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    auto& w = c->win;
-    const int K = cfg->K, NF = K + 2;
-    int nmax, nblk_max, x0max;
-    vil_prior_capacity(K, &nmax, &nblk_max, &x0max);
-    if (!w.open || w.K != K || w.T != cfg->max_tracks || w.S != cfg->max_samples) {
-        hipFree(w.d_store); hipFree(w.d_samp); hipFree(w.d_hdr); hipFree(w.d_rec); hipFree(w.d_U); hipFree(w.d_prior[0]); hipFree(w.d_prior[1]);
-        w.d_store = w.d_samp = w.d_hdr = w.d_rec = w.d_U = w.d_prior[0] = w.d_prior[1] = nullptr; w.open = false;
-        w.K = K; w.T = cfg->max_tracks; w.S = cfg->max_samples; w.NF = NF; w.nmax = nmax; w.x0max = x0max;
-        HIPCHK(hipMalloc(&w.d_store, 8 * (size_t)NF * w.T * VIL_WIN_OBS));
-        HIPCHK(hipMalloc(&w.d_samp, 8 * (size_t)NF * 7 * w.S)); HIPCHK(hipMalloc(&w.d_hdr, 8 * (size_t)NF * 12));
-        HIPCHK(hipMalloc(&w.d_rec, 8 * (size_t)NF * 287)); HIPCHK(hipMalloc(&w.d_U, 8 * (size_t)NF * 225));
-        for (int q = 0; q < 2; ++q) HIPCHK(hipMalloc(&w.d_prior[q], 8 * w.prior_doubles()));
-        if (!w.d_wstat) HIPCHK(hipMalloc(&w.d_wstat, 64));
-    }
-    HIPCHK(hipMemsetAsync(w.d_store, 0, 8 * (size_t)NF * w.T * VIL_WIN_OBS, c->stream));
-    HIPCHK(hipMemsetAsync(w.d_rec, 0, 8 * (size_t)NF * 287, c->stream)); HIPCHK(hipMemsetAsync(w.d_U, 0, 8 * (size_t)NF * 225, c->stream));
-    HIPCHK(hipMemsetAsync(w.d_wstat, 0, 64, c->stream));
-    w.cfg = *cfg; w.open = true;
-    w.fslot.clear(); w.islot.clear(); w.free_f.clear(); w.free_i.clear();
-    for (int q = NF - 1; q >= 0; --q) { w.free_f.push_back(q); w.free_i.push_back(q); }
-    w.ns.assign(NF, 0); w.sum_dt.assign(NF, 0.0);
-    w.cur = 0; w.pn = 0; w.pm = 0; w.pkind.clear(); w.pindex.clear(); w.pcol.clear();
-    c->uploaded = false; c->resident_kind = 0;
+    const int st = c->win.open(c->stream, cfg);
+    if (st != VIL_OK) return st;
+    c->invalidate();
     return vil_lidar_reset(c);
 }
 
 int vil_win_push_frame(vil_ctx* c, const vil_win_frame* f) {
-    if (!c || !f || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
-    auto& w = c->win;
-    if ((int)w.fslot.size() >= w.K || f->n_samples < 0 || f->n_samples > w.S || f->n_obs < 0 || f->n_obs > w.T) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c || !f || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
+    Window& w = c->win;
+    if (w.frames() >= w.K || f->n_samples < 0 || f->n_samples > w.S || f->n_obs < 0 || f->n_obs > w.T) return VIL_ERR_INVALID_ARGUMENT;
     if ((f->n_samples > 0 && (!f->dt || !f->acc || !f->gyr)) || (f->n_obs > 0 && (!f->obs_track || !f->obs))) return VIL_ERR_INVALID_ARGUMENT;
     for (int q = 0; q < f->n_obs; ++q) if (f->obs_track[q] < 0 || f->obs_track[q] >= w.T) return VIL_ERR_INVALID_ARGUMENT;
     // (the LiDAR arguments are checked BEFORE the frame / IMU slots are committed: a frame whose points fail must not leave fslot one entry ahead of
     //  the slabs -- "slab i <-> pose K - count + i" would then attach every later frame's points to the wrong pose)
     if (f->n_plane < 0 || f->n_edge < 0 || (f->n_plane > 0 && !f->plane_const) || (f->n_edge > 0 && !f->edge_const)) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    const int ns = f->n_samples, no = f->n_obs;
-    // one staging block, one DMA: [hdr 12 | dt | acc | gyr | observations | track slots]
-    const size_t o_samp = 0, o_obs = 8 * (size_t)(12 + 7 * ns), o_trk = o_obs + 8 * (size_t)no * VIL_WIN_OBS, total = o_trk + 4 * (size_t)no + 64;
-    if (w.pending) { HIPCHK(hipEventSynchronize(w.ev)); w.pending = false; }     // the previous frame's DMA has left the pinned block
-    if (total > w.stage_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (w.h_stage) hipHostFree(w.h_stage); hipFree(w.d_stage); w.h_stage = nullptr; w.d_stage = nullptr; w.stage_cap = 0;
-        const size_t cap = 2 * total + 4096;
-        HIPCHK(hipHostMalloc((void**)&w.h_stage, cap, hipHostMallocDefault)); HIPCHK(hipMalloc(&w.d_stage, cap));
-        w.stage_cap = cap;
-    }
-    double* hs = (double*)(w.h_stage + o_samp);
-    memcpy(hs, f->acc0, 24); memcpy(hs + 3, f->gyr0, 24); memcpy(hs + 6, f->lin_ba, 24); memcpy(hs + 9, f->lin_bg, 24);
-    double sum = 0.0;
-    if (ns) { memcpy(hs + 12, f->dt, 8 * (size_t)ns); memcpy(hs + 12 + ns, f->acc, 24 * (size_t)ns); memcpy(hs + 12 + 4 * (size_t)ns, f->gyr, 24 * (size_t)ns); for (int q = 0; q < ns; ++q) sum += f->dt[q]; }
-    if (no) { memcpy(w.h_stage + o_obs, f->obs, 8 * (size_t)no * VIL_WIN_OBS); memcpy(w.h_stage + o_trk, f->obs_track, 4 * (size_t)no); }
-    HIPCHK(hipMemcpyAsync(w.d_stage, w.h_stage, o_trk + 4 * (size_t)no, hipMemcpyHostToDevice, c->stream));
-    if (!w.ev) HIPCHK(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(w.ev, c->stream)); w.pending = true;
-    const int fs = w.free_f.back(), is = w.free_i.back();
-    w.free_f.pop_back(); w.free_i.pop_back();
-    WinFrameIn A;
-    A.n_obs = no; A.track = (const int*)(w.d_stage + o_trk); A.obs = (const double*)(w.d_stage + o_obs); A.store = w.d_store; A.T = w.T; A.fslot = fs;
-    A.ns = ns; A.samp = (const double*)(w.d_stage + o_samp); A.hdr = w.d_hdr + 12 * (size_t)is; A.dt = w.dt(is); A.acc = w.acc(is); A.gyr = w.gyr(is);
-    const int nbo = (no * VIL_WIN_OBS + 255) / 256;
-    hipLaunchKernelGGL(k_win_frame_in, dim3(nbo + 1), dim3(256), 0, c->stream, A, nbo);
-    if (ns > 0) {                                        // the interval's record and its sqrt-information, where the solver will read them
-        vpre_launch_slot(c->stream, ns, w.dt(is), w.acc(is), w.gyr(is), w.d_hdr + 12 * (size_t)is, w.cfg.noise, w.d_rec + 287 * (size_t)is);
-        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, c->stream, w.d_rec + 287 * (size_t)is, w.d_U + 225 * (size_t)is, w.d_wstat, 1);
-    }
-    w.fslot.push_back(fs); w.islot.push_back(is); w.ns[is] = ns; w.sum_dt[is] = sum;
-    c->uploaded = false; c->resident_kind = 0;
+    const int st = w.push_frame(c->stream, f);
+    if (st != VIL_OK) return st;
+    c->invalidate();
     const int lst = vil_lidar_push(c, f->n_plane, f->plane_const, f->n_edge, f->edge_const);
-    if (lst != VIL_OK) {                                 // (an allocation failed): the frame is taken back -- slots returned, nothing refers to what the kernels above wrote
-        w.fslot.pop_back(); w.islot.pop_back(); w.free_f.push_back(fs); w.free_i.push_back(is);
-    }
+    if (lst != VIL_OK) w.unpush_frame();                 // (an allocation failed): the frame is taken back -- slots returned, nothing refers to what its kernels wrote
     return lst;
 }
 
 int vil_win_drop_frame(vil_ctx* c, int32_t flag) {
-    if (!c || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
-    auto& w = c->win;
-    const int n = (int)w.fslot.size();
-    if (n < 2) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
+    if (c->win.frames() < 2) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    c->uploaded = false; c->resident_kind = 0;
-    if (flag == VIL_MARGIN_OLD) {
-        // frame 0 leaves.  Its IMU slot held the interval that ENDED in it -- not a factor of the window; the interval (0, 1) stays with frame 1
-        w.free_f.push_back(w.fslot[0]); w.free_i.push_back(w.islot[0]);
-        w.fslot.erase(w.fslot.begin()); w.islot.erase(w.islot.begin());
-        return vil_lidar_drop(c, 0);
-    }
-    // MARGIN_SECOND_NEW (estimator.cpp:1754-1786): frame n-2 leaves; the newest frame takes its place and its samples continue the interval
-    // that ended in n-2 (same first measurement, same linearisation point): appended on the device, re-integrated, re-factored
-    const int ia = w.islot[n - 2], ib = w.islot[n - 1];
-    if (w.ns[ia] + w.ns[ib] > w.S) return VIL_ERR_UNSUPPORTED;
-    if (w.ns[ib] > 0) {
-        hipLaunchKernelGGL(k_win_append, dim3(1), dim3(256), 0, c->stream, w.dt(ia), w.acc(ia), w.gyr(ia), w.ns[ia], w.dt(ib), w.acc(ib), w.gyr(ib), w.ns[ib]);
-        w.ns[ia] += w.ns[ib]; w.sum_dt[ia] += w.sum_dt[ib];
-        vpre_launch_slot(c->stream, w.ns[ia], w.dt(ia), w.acc(ia), w.gyr(ia), w.d_hdr + 12 * (size_t)ia, w.cfg.noise, w.d_rec + 287 * (size_t)ia);
-        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, c->stream, w.d_rec + 287 * (size_t)ia, w.d_U + 225 * (size_t)ia, w.d_wstat, 1);
-    }
-    w.free_f.push_back(w.fslot[n - 2]); w.free_i.push_back(ib);
-    w.fslot.erase(w.fslot.begin() + (n - 2));            // the newest frame's observations and LiDAR points stay where they are
-    w.islot.erase(w.islot.begin() + (n - 1));            // ... and it now ends the merged interval
-    return vil_lidar_drop(c, n - 2);
+    c->invalidate();
+    int slab = 0;
+    const int st = c->win.drop_frame(c->stream, flag, &slab);
+    return st != VIL_OK ? st : vil_lidar_drop(c, slab);
 }
 
 int vil_win_solve(vil_ctx* c, const vil_win_problem* wp, vil_state* s, const vil_options* o, vil_summary* sum) {
-    if (!c || !wp || !s || !o || !sum || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
-    auto& w = c->win;
+    if (!c || !wp || !s || !o || !sum || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
+    const Window& w = c->win;
     const int K = w.K, L = wp->L;
-    if ((int)w.fslot.size() != K || L < 0 || s->K != K || s->L != L) return VIL_ERR_INVALID_ARGUMENT;
+    if (w.frames() != K || L < 0 || s->K != K || s->L != L) return VIL_ERR_INVALID_ARGUMENT;
     if (L > 0 && (!wp->lm_track || !wp->lm_start || !wp->lm_nobs)) return VIL_ERR_INVALID_ARGUMENT;
     int n_vis = 0;
     for (int l = 0; l < L; ++l) {
@@ -2292,15 +2115,14 @@ int vil_win_solve(vil_ctx* c, const vil_win_problem* wp, vil_state* s, const vil
     int imu_i[VIL_WIN_MAXK], imu_j[VIL_WIN_MAXK];
     for (int k = 0; k + 1 < K; ++k) { imu_i[k] = k; imu_j[k] = k + 1; }
     q.n_imu = K - 1; q.imu_i = imu_i; q.imu_j = imu_j; q.imu_const = nullptr;
-    q.prior.n = w.pn; q.prior.nblk = (int)w.pkind.size(); q.prior.blk_kind = w.pkind.data(); q.prior.blk_index = w.pindex.data(); q.prior.blk_col = w.pcol.data();
+    w.prior_blocks(q.prior);
     q.n_icp = wp->n_icp; q.icp_ids = wp->icp_ids; q.icp_const = wp->icp_const; q.n_lps = wp->n_lps; q.lps_ids = wp->lps_ids; q.lps_const = wp->lps_const;
     q.n_plane = q.n_edge = VIL_LIDAR_RESIDENT;
     memcpy(q.q_lb, w.cfg.q_lb, sizeof q.q_lb); memcpy(q.t_lb, w.cfg.t_lb, sizeof q.t_lb); memcpy(q.G, w.cfg.G, sizeof q.G);
     q.sqrt_info_px = w.cfg.sqrt_info_px; q.tr_over_row = w.cfg.tr_over_row;
     WinSrc ws; memset(&ws, 0, sizeof ws);
-    ws.lm_track = wp->lm_track; ws.lm_startf = wp->lm_start; ws.lm_nobs = wp->lm_nobs; ws.n_vis = n_vis; ws.T = w.T;
-    ws.d_store = w.d_store; ws.fslot = w.fslot.data(); ws.islot = w.islot.data(); ws.d_rec = w.d_rec; ws.d_U = w.d_U; ws.sum_dt = w.sum_dt.data();
-    ws.pJ0 = w.pJ0(w.cur); ws.pr0 = w.pr0(w.cur); ws.px0 = w.px0(w.cur); ws.pH = w.pH(w.cur); ws.pg0 = w.pg0(w.cur); ws.pc0 = w.pc0(w.cur);
+    ws.lm_track = wp->lm_track; ws.lm_startf = wp->lm_start; ws.lm_nobs = wp->lm_nobs; ws.n_vis = n_vis;
+    w.fill(ws);
     ws.lb = 0; ws.le = L; ws.f0 = 0; ws.n_vis_all = n_vis;
     // vil_win_solve returns the gauge-fixed state and vil_win_marginalize linearises at it (double2vector() precedes the marginalisation,
     // estimator.cpp:1419 / :1487): the device gauge fix is part of the resident window whatever vil_set_gauge_fix was left at
@@ -2323,7 +2145,7 @@ int vil_win_solve(vil_ctx* c, const vil_win_problem* wp, vil_state* s, const vil
     } else st = upload_impl(c, &q, s, false, nullptr, nullptr, 0, false, &ws);
     if (st != VIL_OK) { c->gauge_on = gauge_was; return st; }
     c->resident_kind = 1;
-    c->P.setup_stat = w.d_wstat;                       // the window's sticky status word: a failed pre-integration / prior ends the solve with it
+    c->P.setup_stat = w.status_word();                      // the window's sticky status word: a failed pre-integration / prior ends the solve with it
     const auto t1 = std::chrono::steady_clock::now();
     st = vil_solve_resident(c, o, sum);
     c->gauge_on = gauge_was;                           // (the caller's setting governs vil_solve / vil_solve_resident of other uploads again)
@@ -2336,59 +2158,21 @@ int vil_win_solve(vil_ctx* c, const vil_win_problem* wp, vil_state* s, const vil
 }
 
 int vil_win_marginalize(vil_ctx* c, const vil_options* o, const vil_marg_spec* spec, vil_win_prior_info* info) {
-    if (!c || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
     return marginalize_resident_impl(c, nullptr, o, spec, nullptr, true, info);
 }
 
 int vil_win_prior_download(vil_ctx* c, vil_prior_out* out) {
-    if (!c || !out || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
-    auto& w = c->win;
+    if (!c || !out || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    int& wst = c->h_word[8]; wst = 0;
-    HIPCHK(hipMemcpyAsync(&wst, w.d_wstat, 4, hipMemcpyDeviceToHost, c->stream));
-    out->n = w.pn; out->nblk = (int)w.pkind.size(); out->m = w.pm;
-    if (w.pn > 0) {
-        const size_t n = (size_t)w.pn;
-        int xo = 0;
-        for (size_t b = 0; b < w.pkind.size(); ++b) { out->blk_kind[b] = w.pkind[b]; out->blk_index[b] = w.pindex[b]; out->blk_col[b] = w.pcol[b]; xo += (w.pkind[b] == VIL_BLK_POSE || w.pkind[b] == VIL_BLK_EX) ? 7 : (w.pkind[b] == VIL_BLK_SPEEDBIAS ? 9 : 1); }
-        HIPCHK(hipMemcpyAsync(out->J0, w.pJ0(w.cur), 8 * n * n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(out->r0, w.pr0(w.cur), 8 * n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(out->x0, w.px0(w.cur), 8 * (size_t)xo, hipMemcpyDeviceToHost, c->stream));
-        if (out->A) HIPCHK(hipMemcpyAsync(out->A, w.pH(w.cur), 8 * n * n, hipMemcpyDeviceToHost, c->stream));      // J0^T J0
-        if (out->b) HIPCHK(hipMemcpyAsync(out->b, w.pg0(w.cur), 8 * n, hipMemcpyDeviceToHost, c->stream));          // J0^T r0
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipGetLastError());
-    return wst;
+    return c->win.prior_download(c->stream, out, &c->h_word[8]);
 }
 
 int vil_win_prior_set(vil_ctx* c, const vil_prior* pr) {
-    if (!c || !c->win.open) return VIL_ERR_INVALID_ARGUMENT;
-    auto& w = c->win;
+    if (!c || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    if (!pr || pr->n <= 0) { w.pn = 0; w.pm = 0; w.pkind.clear(); w.pindex.clear(); w.pcol.clear(); return VIL_OK; }
-    if (pr->n > w.nmax || pr->nblk <= 0 || pr->nblk > VIL_WIN_MAXBLK || !pr->blk_kind || !pr->blk_index || !pr->blk_col || !pr->x0 || !pr->J0 || !pr->r0) return VIL_ERR_INVALID_ARGUMENT;
-    const size_t n = (size_t)pr->n;
-    int xo = 0;
-    for (int b = 0; b < pr->nblk; ++b) xo += (pr->blk_kind[b] == VIL_BLK_POSE || pr->blk_kind[b] == VIL_BLK_EX) ? 7 : (pr->blk_kind[b] == VIL_BLK_SPEEDBIAS ? 9 : 1);
-    if (xo > w.x0max) return VIL_ERR_INVALID_ARGUMENT;
-    const int dst = 1 - w.cur;
-    // stage J0 | r0 in the marginalisation work space layout k_prior_commit reads, x0 directly
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(w.pJ0(dst), pr->J0, 8 * n * n, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(w.pr0(dst), pr->r0, 8 * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(w.px0(dst), pr->x0, 8 * (size_t)xo, hipMemcpyHostToDevice));
-    PriorCommit pc; memset(&pc, 0, sizeof pc);
-    pc.n = pr->n; pc.nblk = 0; pc.J0 = w.pJ0(dst); pc.r0 = w.pr0(dst); pc.x = nullptr; pc.K = w.K;      // nblk = 0: x0 already in place
-    pc.pJ0 = w.pJ0(dst); pc.pr0 = w.pr0(dst); pc.px0 = w.px0(dst); pc.pH = w.pH(dst); pc.pg0 = w.pg0(dst); pc.pc0 = w.pc0(dst); pc.status = w.d_wstat;
-    {
-        const size_t pl = 8 * (n * (n + 1) + n + 8);
-        if (pl > 48 * 1024) HIPCHK(grant_lds(c, (const void*)k_prior_commit, pl));
-        hipLaunchKernelGGL(k_prior_commit, dim3(16), dim3(256), pl, c->stream, pc);
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    w.cur = dst; w.pn = pr->n; w.pm = 0;
-    w.pkind.assign(pr->blk_kind, pr->blk_kind + pr->nblk); w.pindex.assign(pr->blk_index, pr->blk_index + pr->nblk); w.pcol.assign(pr->blk_col, pr->blk_col + pr->nblk);
-    return VIL_OK;
+    if (pr && pr->n > 0 && (pr->n > c->win.nmax || pr->nblk <= 0 || pr->nblk > VIL_WIN_MAXBLK || !pr->blk_kind || !pr->blk_index || !pr->blk_col || !pr->x0 || !pr->J0 || !pr->r0)) return VIL_ERR_INVALID_ARGUMENT;
+    return c->win.prior_set(c->stream, pr);      // (a prior whose x0 exceeds the slot's capacity is an invalid argument as well)
 }
 
 // ---- multi-GPU set-up (vil_comm.hpp): installing a transport releases whatever the context had, and invalidates the resident problem
@@ -2420,7 +2204,7 @@ int vil_comm_init_local(vil_ctx** ctxs, int n) {
 }
 
 // ---- the lab bench (include/vilsolve_debug.h): test hooks and the profilers of the kernels' role layout ------------------------------------------
-int vil_debug_set_launch_mode(vil_ctx* c, int32_t mode) { if (!c || mode < 0 || mode > 4) return VIL_ERR_INVALID_ARGUMENT; c->launch_mode = mode; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
+int vil_debug_set_launch_mode(vil_ctx* c, int32_t mode) { if (!c || mode < 0 || mode > 4) return VIL_ERR_INVALID_ARGUMENT; c->launch_mode = mode; c->invalidate(); return VIL_OK; }
 int vil_debug_get_launch_structure(vil_ctx* c, int32_t* launches_per_iteration, int32_t* one_launch) {
     if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
     const int rung = top_rung(c);
@@ -2434,7 +2218,7 @@ int vil_debug_drop_flag(vil_ctx* c, int32_t role, int32_t launch) {
     c->drop_role = role; c->drop_launch = launch;
     return VIL_OK;
 }
-int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->uploaded = false; c->resident_kind = 0; return VIL_OK; }
+int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->invalidate(); return VIL_OK; }
 int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->comm.slim_emul = on != 0; return VIL_OK; }
 int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) {
     if (!c || !A || !L || !x || !ok || D < 1 || D > 159 || variant < 0 || variant > 1) return VIL_ERR_INVALID_ARGUMENT;

@@ -77,3 +77,42 @@ def test_resident_entry_points_reject_misuse():
     be.lidar_drop(0)
     be.solve(w, rp.opts)                                     # ten slabs: fine
     be.close()
+
+
+def test_slab_tables_grow_with_live_slabs():
+    """The per-slab capacity grows twice while earlier slabs are live (their points are copied into the new tables), and a fifth push grows the slot
+    count: every solve equals vil_solve handed the same truncated point sets."""
+    K = 4
+    rp = replay.Replay(K=K, n_frames=K + 4, L=60, n_plane=4 * 1100, n_edge=4 * 560, seed=5, max_iterations=8)
+    cut = [(200, 100), (600, 300), (1100, 560), (1100, 560)]             # plane: 256 -> 768 -> 1536 points per slab, edge: 256 -> 512 -> 768
+    sets = [(rp.lidar[k][0][:np_], rp.lidar[k][1][:ne]) for k, (np_, ne) in enumerate(cut)]
+    fifth = (rp.lidar[K - 1][0][:900], rp.lidar[K - 1][1][:450])
+    be = lib.open_vilsolve()
+
+    def classic(frames):
+        w = rp.window()
+        w.plane_pose = np.concatenate([np.full(len(p), k, np.int32) for k, (p, e) in enumerate(frames)]); w.plane_const = np.concatenate([p for p, e in frames])
+        w.edge_pose = np.concatenate([np.full(len(e), k, np.int32) for k, (p, e) in enumerate(frames)]); w.edge_const = np.concatenate([e for p, e in frames])
+        p0 = w.pose[0].copy()
+        sm = be.solve(w, rp.opts); be.gauge_fix(p0, w)
+        return sm.iterations, w.pose.copy(), w.speedbias.copy(), w.inv_depth.copy()
+
+    def resident():
+        w = rp.window(with_lidar=False)
+        sm = be.solve(w, rp.opts)                                # comes back gauge-fixed
+        return sm.iterations, w.pose.copy(), w.speedbias.copy(), w.inv_depth.copy()
+
+    def same(ra, rb):
+        assert ra[0] == rb[0], (ra[0], rb[0])
+        assert np.abs(ra[1] - rb[1]).max() < 1e-8 and np.abs(ra[2] - rb[2]).max() < 1e-7, np.abs(ra[1] - rb[1]).max()
+        assert np.abs(ra[3] - rb[3]).max() < 1e-7
+    after = sets[:K - 1] + [fifth]
+    ref = classic(sets), classic(after)
+    be.set_gauge_fix(True); be.lidar_reset()
+    for p, e in sets:
+        be.lidar_push(p, e)
+    same(ref[0], resident())
+    be.lidar_push(*fifth)                                        # no free slot: the tables grow to eight slots with four live slabs
+    be.lidar_drop(K - 1)
+    same(ref[1], resident())
+    be.close()

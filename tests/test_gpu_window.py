@@ -114,6 +114,95 @@ def test_resident_window_rejects_misuse():
     be.close()
 
 
+def test_win_prior_set_round_trip():
+    """vil_win_prior_set: a prior handed back to a re-opened window is the prior the chain had committed -- the tables and the square root bit for bit,
+    the contractions k_prior_commit recomputes from it, and the solve that reads the slot equals vil_solve with the same prior in host tables."""
+    K = 8
+    rp = replay.Replay(K=K, n_frames=K + 8, L=60, n_plane=320, n_edge=80, seed=11, max_iterations=8)
+    be = lib.open_vilsolve()
+    _open(be, rp)
+    P = None
+    for _ in range(6):                                                  # until win_marginalize has committed a prior
+        flag = rp.margin_flag(); w = rp.win_window()
+        be.win_solve(w, rp.opts)
+        info = be.win_marginalize(flag, w._icp_marg, w._lps_marg, rp.opts)
+        P = be.win_prior_download(K)
+        be.win_drop_frame(flag)
+        assert rp.absorb(w, P, flag)                                    # rp.prior = P.to_prior()
+        be.win_push_frame(rp.win_frame(K - 1))
+        if info.n > 0:
+            break
+    n, nb = P.c.n, P.c.nblk
+    assert n > 0 and nb > 0
+    ng = sum({0: 7, 1: 9, 2: 7, 3: 1}[int(k)] for k in P.blk_kind[:nb])
+    _open(be, rp)                                                       # the same frames in a fresh window: no prior
+    assert be.win_prior_download(K).c.n == 0
+    be.win_prior_set(P.to_prior())
+    Q = be.win_prior_download(K)
+    assert Q.c.n == n and Q.c.nblk == nb
+    assert np.array_equal(Q.blk_kind[:nb], P.blk_kind[:nb]) and np.array_equal(Q.blk_index[:nb], P.blk_index[:nb]) and np.array_equal(Q.blk_col[:nb], P.blk_col[:nb])
+    assert np.array_equal(Q.J0[:n * n], P.J0[:n * n]) and np.array_equal(Q.r0[:n], P.r0[:n]) and np.array_equal(Q.x0[:ng], P.x0[:ng])
+    Aq, Jq = Q.A_matrix(), Q.to_prior().J_matrix()
+    dA, db = np.abs(Jq.T @ Jq - Aq).max(), np.abs(Jq.T @ Q.r0[:n] - Q.b_vector()).max()
+    print("prior_set round trip: n %d, max|A| %.3e, |J0^T J0 - A| %.3e, |J0^T r0 - b| %.3e" % (n, np.abs(Aq).max(), dA, db))
+    assert dA < 1e-9 * np.abs(Aq).max()
+    assert db < 1e-9 * np.abs(Aq).max()
+    w = rp.win_window()
+    wc = Window.from_dict(rp.window().to_dict())                        # every table on the host, the same prior
+    assert wc.prior.n == n
+    p0 = wc.pose[0].copy()
+    sg = be.win_solve(w, rp.opts)                                       # comes back gauge-fixed
+    bc = lib.open_vilsolve()
+    sc = bc.solve(wc, rp.opts); bc.gauge_fix(p0, wc)
+    bc.close()
+    assert sg.iterations == sc.iterations, (sg.iterations, sc.iterations)
+    assert np.abs(w.pose - wc.pose).max() < 1e-7 and np.abs(w.inv_depth - wc.inv_depth).max() < 1e-6, np.abs(w.pose - wc.pose).max()
+    be.win_prior_set(None)
+    assert be.win_prior_download(K).c.n == 0
+    good = P.to_prior()
+    with pytest.raises(lib.VilError):
+        be.win_prior_set(abi.Prior(n, (), (), (), good.x0, good.J0, good.r0))       # nblk == 0
+    nbig = 6 * K + 16 + 1                                               # one above the window's capacity (vil_prior_capacity)
+    with pytest.raises(lib.VilError):
+        be.win_prior_set(abi.Prior(nbig, good.blk_kind, good.blk_index, good.blk_col, good.x0, np.zeros(nbig * nbig), np.zeros(nbig)))
+    assert be.win_prior_download(K).c.n == 0                            # a refused prior leaves the slot as it was
+    be.close()
+
+
+def test_resident_window_reopen_with_other_dimensions():
+    """vil_win_open on an open window with another max_tracks: the store is released and allocated again; the chain that follows equals the classic one."""
+    kw = dict(K=8, n_frames=14, L=60, n_plane=320, n_edge=80, seed=7, max_iterations=8)
+    be = lib.open_vilsolve()
+    rc = replay.Replay(**kw)
+    ref = []
+    for _ in range(3):
+        w = rc.window(); flag = rc.margin_flag(); p0 = w.pose[0].copy()
+        sm = be.solve(w, rc.opts); be.gauge_fix(p0, w)
+        pg = be.marginalize(w, flag, w._icp_marg, w._lps_marg, rc.opts)
+        ref.append((sm.iterations, w.pose.copy(), w.inv_depth.copy()))
+        assert rc.absorb(w, pg, flag)
+    rp = replay.Replay(**kw)
+    args = rp.win_open_args()
+    assert max(tr.slot for tr in rp.tracks) < args["max_tracks"] // 2
+    be.set_gauge_fix(True)
+    be.win_open(**dict(args, max_tracks=args["max_tracks"] // 2))
+    for k in range(rp.K):
+        be.win_push_frame(rp.win_frame(k))
+    be.win_open(**args)                                                 # other dimensions: every table of the store is new
+    for k in range(rp.K):
+        be.win_push_frame(rp.win_frame(k))
+    for f in range(3):
+        w = rp.win_window(); flag = rp.margin_flag()
+        sm = be.win_solve(w, rp.opts)
+        be.win_marginalize(flag, w._icp_marg, w._lps_marg, rp.opts)
+        assert sm.iterations == ref[f][0], (f, sm.iterations, ref[f][0])
+        assert np.abs(w.pose - ref[f][1]).max() < 1e-7 and np.abs(w.inv_depth - ref[f][2]).max() < 1e-6, (f, np.abs(w.pose - ref[f][1]).max())
+        be.win_drop_frame(flag)
+        assert rp.absorb(w, None, flag)
+        be.win_push_frame(rp.win_frame(rp.K - 1))
+    be.close()
+
+
 def test_resident_window_k20_chain_in_sweep(oracle):
     """K = 20: beyond the merged gather + step launch -- the chain workgroup rides in k_sweep, the W W^T tiles in k_reduce (vil_prechain.hpp)."""
     K = 20
