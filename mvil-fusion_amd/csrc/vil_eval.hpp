@@ -31,6 +31,20 @@ __global__ void k_eval_visual(DevP P, const double* x, double* r, double* J) {
     w[42] = o.Jl[0]; w[43] = o.Jl[1]; w[44] = o.Jt[0]; w[45] = o.Jt[1];
 }
 
+// EDGE (nr = 3: c = cp a b) or PLANE-NORM (nr = 1: c = cp n d) of one point at one pose, OUT OF LINE, called by k_eval_lidar and k_eval_lidar_functors
+// alike so that functor kinds 0 and 2 return the window classes' bits: inlined into each kernel, quatR and the products after it are contracted into
+// different fused multiply-adds per kernel (up to 3e-13 of the residual's size apart).  noinline does not forbid the compiler to clone or specialise
+// this body (nr is a constant in one caller): that both callers run one body is an observed property of the build, held by
+// tests/test_gpu_factors_floor.py, not a guarantee of the language.  Arguments travel through private arrays; neither kernel is on the hot path,
+// and the sweep keeps its own inlined edge_eval / plane_eval.
+__device__ __attribute__((noinline)) void lidar_point_eval(int nr, const double* c, const double* Rbl9, const double* tbl3, const double* pose7, double* rr, double* JJ) {
+    using namespace vd;
+    const M3 R = quatR(pose7 + 3), Rbl = loadM3(Rbl9);
+    const V3 Pk{pose7[0], pose7[1], pose7[2]}, tbl{tbl3[0], tbl3[1], tbl3[2]};
+    if (nr == 1) plane_eval(V3{c[0], c[1], c[2]}, V3{c[3], c[4], c[5]}, c[6], Rbl, tbl, R, Pk, rr[0], JJ);
+    else edge_eval(V3{c[0], c[1], c[2]}, V3{c[3], c[4], c[5]}, V3{c[6], c[7], c[8]}, Rbl, tbl, R, Pk, rr, JJ);
+}
+
 template <int NR>
 __global__ void k_eval_lidar(DevP P, const double* x, double* r, double* J) {
     using namespace vd;
@@ -42,12 +56,14 @@ __global__ void k_eval_lidar(DevP P, const double* x, double* r, double* J) {
     int lo = 0, hi = (NR == 1 ? P.n_pchunk : P.n_echunk) - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ch[3 * mid] <= f) lo = mid; else hi = mid - 1; }
     const int k = ch[3 * lo + 2];
-    const double* pose = x + xo_pose(P, k);
-    const M3 R = quatR(pose + 3), Rbl = loadM3(P.Rbl);
-    const V3 Pk{pose[0], pose[1], pose[2]}, tbl{P.tbl[0], P.tbl[1], P.tbl[2]};
-    double rr[NR], JJ[NR * 6];
-    if (NR == 1) { const double* c = P.pl_c; const int s = P.pl_stride; plane_eval(V3{c[f], c[s + f], c[2 * s + f]}, V3{c[3 * s + f], c[4 * s + f], c[5 * s + f]}, c[6 * s + f], Rbl, tbl, R, Pk, rr[0], JJ); }
-    else { const double* c = P.ed_c; const int s = P.ed_stride; edge_eval(V3{c[f], c[s + f], c[2 * s + f]}, V3{c[3 * s + f], c[4 * s + f], c[5 * s + f]}, V3{c[6 * s + f], c[7 * s + f], c[8 * s + f]}, Rbl, tbl, R, Pk, rr, JJ); }
+    double pose[7], cc[9], Rb[9], tb[3], rr[3], JJ[18];
+    for (int q = 0; q < 7; ++q) pose[q] = x[xo_pose(P, k) + q];
+    for (int q = 0; q < 9; ++q) Rb[q] = P.Rbl[q];
+    for (int q = 0; q < 3; ++q) tb[q] = P.tbl[q];
+    const double* c = NR == 1 ? P.pl_c : P.ed_c;
+    const int s = NR == 1 ? P.pl_stride : P.ed_stride;
+    for (int q = 0; q < (NR == 1 ? 7 : 9); ++q) cc[q] = c[(size_t)q * s + f];
+    lidar_point_eval(NR, cc, Rb, tb, pose, rr, JJ);
     for (int q = 0; q < NR; ++q) {
         r[(size_t)f * NR + q] = rr[q];
         if (J) { for (int c2 = 0; c2 < 6; ++c2) J[((size_t)f * NR + q) * 7 + c2] = JJ[q * 6 + c2]; J[((size_t)f * NR + q) * 7 + 6] = 0.0; }
@@ -60,28 +76,35 @@ __global__ void k_eval_lidar_functors(int kind, int n, const double* __restrict_
     using namespace vd;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
-    const M3 R = quatR(A.pose + 3), Rbl = loadM3(A.Rbl);
-    const V3 Pk{A.pose[0], A.pose[1], A.pose[2]}, tbl{A.tbl[0], A.tbl[1], A.tbl[2]};
     const int nc = kind == 0 ? 9 : (kind == 1 ? 12 : (kind == 2 ? 7 : 6)), nr = (kind == 0 || kind == 3) ? 3 : 1;
     const double* q = c + (size_t)f * nc;
-    const V3 cp{q[0], q[1], q[2]};
     double rr[3] = {0, 0, 0}, JJ[18];
     for (int e = 0; e < 18; ++e) JJ[e] = 0.0;
-    if (kind == 0) edge_eval(cp, V3{q[3], q[4], q[5]}, V3{q[6], q[7], q[8]}, Rbl, tbl, R, Pk, rr, JJ);
-    else if (kind == 1) {                               // LidarPlaneFactor: ljm_norm = ((j - l) x (j - m)).normalized(), residual (lp - j) . ljm_norm
-        const V3 pj{q[3], q[4], q[5]}, pl_{q[6], q[7], q[8]}, pm{q[9], q[10], q[11]};
-        V3 nv = cross(pj - pl_, pj - pm);
-        const double inv = 1.0 / sqrt(dot(nv, nv));
-        nv = inv * nv;
-        plane_eval(cp, nv, -dot(nv, pj), Rbl, tbl, R, Pk, rr[0], JJ);
-    } else if (kind == 2) plane_eval(cp, V3{q[3], q[4], q[5]}, q[6], Rbl, tbl, R, Pk, rr[0], JJ);
-    else {                                              // LidarDistanceFactor: r = p_w - closed ; J = [I | -R [p_b]x]
-        const V3 pb = mul(Rbl, cp) + tbl, pw = mul(R, pb) + Pk;
-        rr[0] = pw.x - q[3]; rr[1] = pw.y - q[4]; rr[2] = pw.z - q[5];
-        for (int i = 0; i < 3; ++i) {
-            const V3 ei{i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0};
-            const V3 jr = cross(pb, mulT(R, ei));         // row i of -R [p_b]x
-            JJ[6 * i + i] = 1.0; JJ[6 * i + 3] = jr.x; JJ[6 * i + 4] = jr.y; JJ[6 * i + 5] = jr.z;
+    if (kind == 0 || kind == 2) {                       // the window's EDGE / PLANE classes: the same code as k_eval_lidar, bit for bit
+        double cc[9], pose[7], Rb[9], tb[3];
+        for (int e = 0; e < nc; ++e) cc[e] = q[e];
+        for (int e = 0; e < 7; ++e) pose[e] = A.pose[e];
+        for (int e = 0; e < 9; ++e) Rb[e] = A.Rbl[e];
+        for (int e = 0; e < 3; ++e) tb[e] = A.tbl[e];
+        lidar_point_eval(nr, cc, Rb, tb, pose, rr, JJ);
+    } else {
+        const M3 R = quatR(A.pose + 3), Rbl = loadM3(A.Rbl);
+        const V3 Pk{A.pose[0], A.pose[1], A.pose[2]}, tbl{A.tbl[0], A.tbl[1], A.tbl[2]};
+        const V3 cp{q[0], q[1], q[2]};
+        if (kind == 1) {                               // LidarPlaneFactor: ljm_norm = ((j - l) x (j - m)).normalized(), residual (lp - j) . ljm_norm
+            const V3 pj{q[3], q[4], q[5]}, pl_{q[6], q[7], q[8]}, pm{q[9], q[10], q[11]};
+            V3 nv = cross(pj - pl_, pj - pm);
+            const double inv = 1.0 / sqrt(dot(nv, nv));
+            nv = inv * nv;
+            plane_eval(cp, nv, -dot(nv, pj), Rbl, tbl, R, Pk, rr[0], JJ);
+        } else {                                            // LidarDistanceFactor: r = p_w - closed ; J = [I | -R [p_b]x]
+            const V3 pb = mul(Rbl, cp) + tbl, pw = mul(R, pb) + Pk;
+            rr[0] = pw.x - q[3]; rr[1] = pw.y - q[4]; rr[2] = pw.z - q[5];
+            for (int i = 0; i < 3; ++i) {
+                const V3 ei{i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0};
+                const V3 jr = cross(pb, mulT(R, ei));         // row i of -R [p_b]x
+                JJ[6 * i + i] = 1.0; JJ[6 * i + 3] = jr.x; JJ[6 * i + 4] = jr.y; JJ[6 * i + 5] = jr.z;
+            }
         }
     }
     for (int i = 0; i < nr; ++i) {
