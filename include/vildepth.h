@@ -11,9 +11,10 @@
  *     pcl::getTransformation -> Affine3f inverse), lidar_to_view is Tlc_ * TransFormLC.inverse() (:134-140).  The caller builds both in
  *     float, exactly as the reference does, and hands over the upper three rows, row-major.  mvil-fusion_amd/depthreg.py::view_matrices
  *     builds them from rotations and translations for the tests.
- *   - lidar_callback's accumulation of depthCloud (feature_tracker_node.cpp:252-337: transform to world, pcl::ApproximateVoxelGrid, the
- *     5 s queue).  pcl::ApproximateVoxelGrid is a hash with eviction whose result depends on its table size and on the order of the
- *     points; this library does not imitate it (see vilscan.h step 6).
+ *   - lidar_callback's accumulation of depthCloud (feature_tracker_node.cpp:252-337: pcl::ApproximateVoxelGrid, the view filter, the
+ *     transform to world, the 5 s queue) is no part of THIS header.  It has a device row of its own, vilcloud.h, whose publish call
+ *     makes its cloud the resident cloud here without a trip through the host; a caller that builds the cloud itself still uploads it
+ *     with the set_cloud call below.
  *
  * ARITHMETIC CONTRACT.  Unfused IEEE float32 in the order written, except where marked double.  p = [x y z intensity].
  *   1 transform   (:132, :140) per row of a matrix m: ((m0*x + m1*y) + m2*z) + m3.  lidar_to_view is applied to the rounded result of

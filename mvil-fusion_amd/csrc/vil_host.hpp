@@ -1,5 +1,5 @@
 // vil_host.hpp -- the host scaffold shared by the row libraries (vilmap.hip, vilvgicp.hip, vilpreint.hip, vilscan.hip, vildepth.hip,
-// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers and the kernel-event profilers.
+// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers and the kernel-event profilers.
 // Header-only, internal linkage: libvilsolve.so exports nothing from here.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -28,6 +28,7 @@
 #include "vil_host.hpp"
 #include "vil_knn.hpp"
 #include "vil_math.hpp"
+#include "vildepth_stage.hpp"
 
 #define VD_BINS VDEPTH_BINS
 #define VD_IMG (VD_BINS * VD_BINS)
@@ -166,6 +167,18 @@ struct vdepth_ctx : vilhost::Device {        // d_mem: cloud | image | row count
     vilhost::Profiler<VDEPTH_NUM_KERNELS, VDEPTH_NUM_KERNELS + 1> prof;
 };
 
+// ---- the hand-over stage (vildepth_stage.hpp) --------------------------------------------------------------------------------------
+vildepth_stage::Target vildepth_stage::target(const vdepth_ctx* c) { return {c->device, c->max_cloud}; }
+int vildepth_stage::replace_cloud(vdepth_ctx* c, const int n, const float* src, const hipMemcpyKind kind) {
+    if (n) {
+        VILCHK(hipSetDevice(c->device));
+        VILCHK(hipMemcpyAsync(c->d_mem + c->o_cloud, src, 16 * (size_t)n, kind, c->stream));
+        VILCHK(hipStreamSynchronize(c->stream));
+    }
+    c->n_cloud = n;
+    return VIL_OK;
+}
+
 extern "C" {
 
 int vdepth_create(int32_t device, int32_t max_cloud_points, int32_t max_features, vdepth_ctx** out) {
@@ -213,14 +226,8 @@ int vdepth_profile_read(vdepth_ctx* c, int64_t* launches3, double* total_ms3) {
 
 int vdepth_set_cloud(vdepth_ctx* c, int32_t n, const float* xyzi) {
     if (!c || n < 0 || n > c->max_cloud || (n && !xyzi)) return VIL_ERR_INVALID_ARGUMENT;
-    if (n) {
-        VILCHK(hipSetDevice(c->device));
-        memcpy(c->h_cloud, xyzi, 16 * (size_t)n);
-        VILCHK(hipMemcpyAsync(c->d_mem + c->o_cloud, c->h_cloud, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        VILCHK(hipStreamSynchronize(c->stream));
-    }
-    c->n_cloud = n;
-    return VIL_OK;
+    if (n) memcpy(c->h_cloud, xyzi, 16 * (size_t)n);
+    return vildepth_stage::replace_cloud(c, n, (const float*)c->h_cloud, hipMemcpyHostToDevice);
 }
 
 int vdepth_register(vdepth_ctx* c, const float* world_to_lidar, const float* lidar_to_view, int32_t n_feat, const float* feat_xyz, float* depth_out, vdepth_summary* out) {
