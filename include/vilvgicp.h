@@ -74,4 +74,6 @@ int vgicp_profile_read(vgicp_ctx* ctx, int64_t* launches, double* total_ms);
 #ifdef __cplusplus
 }
 #endif
+/* the target map built on the device, a resident source promoted to the next target, the map read back in voxel order */
+#include "vilvgicp_voxel.h"
 #endif

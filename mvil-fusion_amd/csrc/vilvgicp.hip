@@ -4,8 +4,9 @@
 //   voxel map of the target (once per scan pair)  |  per LM iteration: correspondences by voxel look-up of every transformed
 //   source point, a 3x3 inverse per correspondence, then a 6x6 / 6x1 / scalar reduction over all correspondences.
 // MI355X-first layout of the same arithmetic:
-//   * target voxel map: built on the host in the reference's sequential order (it is summed once per scan and must not
-//     depend on atomics), stored as an open-addressing table of packed 63-bit voxel keys + SoA voxel records in HBM;
+//   * target voxel map: summed in the reference's sequential order (once per scan; it must not depend on the order atomics arrive in),
+//     on the host (default) or, to the same bits, on the device (build_target_dev below, docs/voxelmap.md), stored as an
+//     open-addressing table of packed 63-bit voxel keys + SoA voxel records in HBM;
 //   * ONE kernel per linearisation: thread = (source point, neighbour offset) does transform, hash probe, RCR inverse,
 //     stores the correspondence (voxel id + Mahalanobis matrix, what compute_error reuses) and its 28 partial sums,
 //     wave64 butterflies + LDS fold them per workgroup, a second tiny kernel adds the workgroup partials in fixed order
@@ -283,6 +284,129 @@ __global__ __launch_bounds__(VG_THREADS) void k_knn_fit(int n, const float* __re
 
 struct HostKeyHash { size_t operator()(long long k) const { return (size_t)hash_key(k) * 2654435761u ^ (size_t)(k >> 17); } };
 
+// ---- the target voxel map on the device (docs/voxelmap.md): GaussianVoxelMap::create_voxelmap's sequential sums, reproduced bit for bit.
+// Membership by an open-addressing table (64-bit compare-and-swap, as vknn::grid_slot); a voxel's number is the count of "first point of
+// its voxel" flags below its first point (atomicMin per slot + a prefix sum over the points); every voxel's members are put into ascending
+// index order by ranking them inside the voxel's run, and one lane per (voxel, component) then adds the run in that order from 0.0 -- the
+// host loop's additions, one by one.  Integer atomics only: which slot a key lands in and where a run lies depend on timing, no result does.
+struct VoxBuild {
+    long long* keys; int* slot_vox; int mask;             // the table being built (the set aside, not the live target)
+    int* cnt; int* cur; int* start; unsigned* first;      // per table slot: members, fill cursor, start of the run, smallest member
+    int* pslot; int* member; int* sorted; int* vstart;    // per point: its slot, the runs as filled, the runs in index order; per voxel: start of its run
+    int* bsum; int* boff;                                 // per 256 points: first-point flags in the block, and in all blocks before it
+    int* ctr;                                             // [0] run cursor, [1] voxels, [2] non-finite flag
+    int* num; double* mean; double* cov; double* wsq;     // the voxel records (SoA, voxel order)
+};
+
+__device__ __forceinline__ long long vox_key_exact(float x, float y, float z, double res) {
+#pragma clang fp contract(off)
+    const double px = (double)x, py = (double)y, pz = (double)z;          // IEEE divide, subtract, floor: the host's expression, operation by operation
+    return pack_key((int)floor(px / res - 0.5), (int)floor(py / res - 0.5), (int)floor(pz / res - 0.5));
+}
+
+// every slot of the table in use empty, the counters zero: nothing of an earlier (larger) build is read again
+__global__ __launch_bounds__(VG_THREADS) void k_vox_clear(int tcap, VoxBuild B) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < 4) B.ctr[e] = 0;
+    if (e >= tcap) return;
+    B.keys[e] = -1LL; B.slot_vox[e] = -1; B.cnt[e] = 0; B.cur[e] = 0; B.first[e] = 0xFFFFFFFFu;
+}
+__global__ __launch_bounds__(VG_THREADS) void k_vox_insert(int n, const float* __restrict__ xyz, double res, VoxBuild B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) { B.pslot[i] = -1; atomicOr(B.ctr + 2, 1); return; }
+    const long long key = vox_key_exact(x, y, z, res);
+    int s = -1;
+    for (unsigned h = hash_key(key) & B.mask;; h = (h + 1) & B.mask) {      // at most n keys in >= 2 n slots: never full
+        long long k = B.keys[h];
+        if (k < 0) k = (long long)atomicCAS((unsigned long long*)(B.keys + h), (unsigned long long)-1LL, (unsigned long long)key);      // a stale -1 is settled here
+        if (k < 0 || k == key) { s = (int)h; break; }
+    }
+    B.pslot[i] = s;
+    atomicAdd(B.cnt + s, 1);
+    atomicMin(B.first + s, (unsigned)i);
+}
+// every occupied slot claims a contiguous run (where it lies is irrelevant, as in vknn::k_grid_offsets)
+__global__ __launch_bounds__(VG_THREADS) void k_vox_offsets(int tcap, VoxBuild B) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= tcap) return;
+    const int c = B.cnt[e];
+    if (c) B.start[e] = atomicAdd(B.ctr, c);
+}
+// members into their runs in arrival order; the block's number of first points for the numbering
+__global__ __launch_bounds__(VG_THREADS) void k_vox_fill(int n, VoxBuild B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = i < n ? B.pslot[i] : -1;
+    if (s >= 0) B.member[B.start[s] + atomicAdd(B.cur + s, 1)] = i;
+    const int firsts = __syncthreads_count(s >= 0 && B.first[s] == (unsigned)i);
+    if (threadIdx.x == 0) B.bsum[blockIdx.x] = firsts;
+}
+// exclusive prefix sum of the block counts by one workgroup, 256 at a time with a carry; the total is the number of voxels
+__global__ __launch_bounds__(VG_THREADS) void k_vox_scan(int nb, VoxBuild B) {
+    __shared__ int wtot[VG_THREADS / 64];
+    __shared__ int carry_sh;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) carry_sh = 0;
+    __syncthreads();
+    for (int base = 0; base < nb; base += VG_THREADS) {
+        const int x = base + t < nb ? B.bsum[base + t] : 0;
+        int incl = x;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); incl += lane >= o ? v : 0; }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        int woff = 0;
+        for (int w = 0; w < wave; ++w) woff += wtot[w];
+        const int carry = carry_sh;
+        if (base + t < nb) B.boff[base + t] = carry + woff + incl - x;
+        __syncthreads();
+        if (t == VG_THREADS - 1) carry_sh = carry + woff + incl;
+        __syncthreads();
+    }
+    if (t == 0) B.ctr[1] = carry_sh;
+}
+// numbering: a voxel's number is the count of first points before its own; ranking: a member's place in its run is the count of smaller members
+__global__ __launch_bounds__(VG_THREADS) void k_vox_rank(int n, VoxBuild B) {
+    __shared__ int wtot[VG_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i = blockIdx.x * blockDim.x + t;
+    const int s = i < n ? B.pslot[i] : -1;
+    const bool is_first = s >= 0 && B.first[s] == (unsigned)i;
+    const unsigned long long bal = __ballot(is_first);
+    if (lane == 0) wtot[wave] = __popcll(bal);
+    __syncthreads();
+    if (s < 0) return;
+    const int b = B.start[s], c = B.cnt[s];
+    if (is_first) {
+        int v = B.boff[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) v += wtot[w];
+        B.slot_vox[s] = v; B.vstart[v] = b; B.num[v] = c; B.wsq[v] = sqrt((double)c);
+    }
+    int r = 0;
+    for (int q = 0; q < c; ++q) r += B.member[b + q] < i ? 1 : 0;
+    B.sorted[b + r] = i;
+}
+// one lane per (voxel, component): 3 of the mean, 9 of the covariance; the run in ascending point index, starting from 0.0
+__global__ __launch_bounds__(VG_THREADS) void k_vox_sum(const float* __restrict__ xyz, const double* __restrict__ cov9, VoxBuild B) {
+#pragma clang fp contract(off)
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int v = (int)(tid / 12), q = (int)(tid - 12 * (long long)v);
+    if (v >= B.ctr[1]) return;
+    const int b = B.vstart[v], c = B.num[v];
+    double acc = 0.0;
+    int u = 0;
+    for (; u + 4 <= c; u += 4) {                          // the loads of four members go out together, the additions stay in order
+        const int i0 = B.sorted[b + u], i1 = B.sorted[b + u + 1], i2 = B.sorted[b + u + 2], i3 = B.sorted[b + u + 3];
+        const double a0 = q < 3 ? (double)xyz[3 * (size_t)i0 + q] : cov9[9 * (size_t)i0 + q - 3], a1 = q < 3 ? (double)xyz[3 * (size_t)i1 + q] : cov9[9 * (size_t)i1 + q - 3];
+        const double a2 = q < 3 ? (double)xyz[3 * (size_t)i2 + q] : cov9[9 * (size_t)i2 + q - 3], a3 = q < 3 ? (double)xyz[3 * (size_t)i3 + q] : cov9[9 * (size_t)i3 + q - 3];
+        acc += a0; acc += a1; acc += a2; acc += a3;
+    }
+    for (; u < c; ++u) { const int i = B.sorted[b + u]; acc += q < 3 ? (double)xyz[3 * (size_t)i + q] : cov9[9 * (size_t)i + q - 3]; }
+    const double m = acc / (double)c;                     // finalize(): the IEEE divide
+    if (q < 3) B.mean[3 * (size_t)v + q] = m; else B.cov[9 * (size_t)v + q - 3] = m;
+}
+
 }  // namespace
 
 struct vgicp_ctx : vilhost::Device {                 // d_mem is d_out; everything else grows on demand
@@ -301,9 +425,18 @@ struct vgicp_ctx : vilhost::Device {                 // d_mem is d_out; everythi
     void* d_coop = nullptr; void* d_aout = nullptr; void* h_aout = nullptr; int coop_epoch = 0;       // one-launch alignment (k_vgicp_align)
     // neighbour search of the covariance estimation
     vknn::GridBuild gb; float grid_h = 1.0f; int grid_min = 4096; int coop_cap = -1; int* d_nn = nullptr; size_t nn_cap = 0;
+    // device builder of the target map (build_target_dev): everything below grows on demand and is never freed between calls
+    int builder = VGICP_BUILD_HOST;
+    int t_alloc = 0, v_alloc = 0;                          // table slots / voxel records the live target's buffers hold
+    struct VoxSet { long long* keys = nullptr; int* slot = nullptr; int* num = nullptr; double* mean = nullptr; double* cov = nullptr; double* wsq = nullptr; int t_alloc = 0, v_alloc = 0; } aside;      // built aside, swapped in when the build succeeded
+    char* d_bws = nullptr; size_t bws_bytes = 0;          // work space of the build
+    float* d_txyz = nullptr; double* d_tcov = nullptr; size_t tpts_cap = 0;       // the target's points and covariances (vgicp_set_target, device builder)
+    int* h_build = nullptr;                                // pinned: voxels | non-finite flag
+    vilhost::Profiler<VGICP_BUILD_KERNELS, VGICP_BUILD_KERNELS + 1> bprof;
 };
 
-static void free_target(vgicp_ctx* c) { hipFree(c->d_keys); hipFree(c->d_slot); hipFree(c->d_num); hipFree(c->d_mean); hipFree(c->d_cov); hipFree(c->d_wsq); c->d_wsq = nullptr; c->d_keys = nullptr; c->d_slot = nullptr; c->d_num = nullptr; c->d_mean = nullptr; c->d_cov = nullptr; c->nvox = 0; }
+static void free_target(vgicp_ctx* c) { hipFree(c->d_keys); hipFree(c->d_slot); hipFree(c->d_num); hipFree(c->d_mean); hipFree(c->d_cov); hipFree(c->d_wsq); c->d_wsq = nullptr; c->d_keys = nullptr; c->d_slot = nullptr; c->d_num = nullptr; c->d_mean = nullptr; c->d_cov = nullptr; c->nvox = 0; c->t_alloc = 0; c->v_alloc = 0; }
+static void free_aside(vgicp_ctx* c) { vgicp_ctx::VoxSet& a = c->aside; hipFree(a.keys); hipFree(a.slot); hipFree(a.num); hipFree(a.mean); hipFree(a.cov); hipFree(a.wsq); a = vgicp_ctx::VoxSet(); }
 static void free_source(vgicp_ctx* c) { hipFree(c->d_sxyz); hipFree(c->d_scov); c->d_sxyz = nullptr; c->d_scov = nullptr; c->n = 0; }
 
 static Iso to_iso(const double* T) { Iso r; for (int q = 0; q < 12; ++q) r.m[q] = T[q]; return r; }
@@ -356,6 +489,55 @@ static hipError_t sum_and_fetch(vgicp_ctx* c, int nblk) {
     return hipStreamSynchronize(c->stream);
 }
 
+// The target map of n device-resident points and covariances, built aside and swapped in: on VIL_ERR_NON_FINITE (or a HIP error) the
+// previous target is untouched.  Seven launches, then ONE host wait for the voxel count and the non-finite flag.
+static int build_target_dev(vgicp_ctx* c, int n, const float* d_xyz, const double* d_cov9, double resolution) {
+    if (n > (1 << 28)) return VIL_ERR_CAPACITY;          // (2 n table slots and 12 n lanes stay below 2^31 with room to spare)
+    int tcap = 64; while (tcap < 2 * n) tcap <<= 1;     // sized from n: the number of voxels is not known on the host
+    vgicp_ctx::VoxSet& a = c->aside;
+    if (a.t_alloc < tcap || a.v_alloc < n) {
+        free_aside(c);
+        const size_t v = (size_t)n + (size_t)n / 2;      // head room: the next scans are about this size
+        VILCHK(hipMalloc(&a.keys, 8 * (size_t)tcap)); VILCHK(hipMalloc(&a.slot, 4 * (size_t)tcap)); VILCHK(hipMalloc(&a.num, 4 * v));
+        VILCHK(hipMalloc(&a.mean, 8 * 3 * v)); VILCHK(hipMalloc(&a.cov, 8 * 9 * v)); VILCHK(hipMalloc(&a.wsq, 8 * v));
+        a.t_alloc = tcap; a.v_alloc = (int)v;
+    }
+    const int nb = (n + VG_THREADS - 1) / VG_THREADS;
+    vilhost::Arena ar;
+    const size_t o_cnt = ar.take(4 * (size_t)tcap), o_cur = ar.take(4 * (size_t)tcap), o_start = ar.take(4 * (size_t)tcap), o_first = ar.take(4 * (size_t)tcap);
+    const size_t o_pslot = ar.take(4 * (size_t)n), o_member = ar.take(4 * (size_t)n), o_sorted = ar.take(4 * (size_t)n), o_vstart = ar.take(4 * (size_t)n);
+    const size_t o_bsum = ar.take(4 * (size_t)nb), o_boff = ar.take(4 * (size_t)nb), o_ctr = ar.take(16);
+    if (ar.bytes > c->bws_bytes) {
+        hipFree(c->d_bws); c->d_bws = nullptr; c->bws_bytes = 0;
+        const size_t want = ar.bytes + ar.bytes / 2;
+        VILCHK(hipMalloc(&c->d_bws, want));
+        c->bws_bytes = want;
+    }
+    char* w = c->d_bws;
+    VoxBuild B{a.keys, a.slot, tcap - 1, (int*)(w + o_cnt), (int*)(w + o_cur), (int*)(w + o_start), (unsigned*)(w + o_first),
+               (int*)(w + o_pslot), (int*)(w + o_member), (int*)(w + o_sorted), (int*)(w + o_vstart), (int*)(w + o_bsum), (int*)(w + o_boff), (int*)(w + o_ctr),
+               a.num, a.mean, a.cov, a.wsq};
+    const dim3 T(VG_THREADS), Gt((tcap + VG_THREADS - 1) / VG_THREADS), Gn(nb), Gs((unsigned)((12 * (size_t)n + VG_THREADS - 1) / VG_THREADS));
+    hipStream_t s = c->stream;
+    VILCHK(c->bprof.mark(0, s)); hipLaunchKernelGGL(k_vox_clear, Gt, T, 0, s, tcap, B);
+    VILCHK(c->bprof.mark(1, s)); hipLaunchKernelGGL(k_vox_insert, Gn, T, 0, s, n, d_xyz, resolution, B);
+    VILCHK(c->bprof.mark(2, s)); hipLaunchKernelGGL(k_vox_offsets, Gt, T, 0, s, tcap, B);
+    VILCHK(c->bprof.mark(3, s)); hipLaunchKernelGGL(k_vox_fill, Gn, T, 0, s, n, B);
+    VILCHK(c->bprof.mark(4, s)); hipLaunchKernelGGL(k_vox_scan, dim3(1), T, 0, s, nb, B);
+    VILCHK(c->bprof.mark(5, s)); hipLaunchKernelGGL(k_vox_rank, Gn, T, 0, s, n, B);
+    VILCHK(c->bprof.mark(6, s)); hipLaunchKernelGGL(k_vox_sum, Gs, T, 0, s, d_xyz, d_cov9, B);
+    VILCHK(c->bprof.mark(7, s));
+    VILCHK(hipMemcpyAsync(c->h_build, B.ctr + 1, 8, hipMemcpyDeviceToHost, s));
+    VILCHK(hipStreamSynchronize(s));
+    VILCHK(hipGetLastError());
+    for (int k = 0; k < VGICP_BUILD_KERNELS; ++k) c->bprof.span(k, k, k + 1);
+    if (c->h_build[1]) return VIL_ERR_NON_FINITE;
+    std::swap(c->d_keys, a.keys); std::swap(c->d_slot, a.slot); std::swap(c->d_num, a.num); std::swap(c->d_mean, a.mean); std::swap(c->d_cov, a.cov); std::swap(c->d_wsq, a.wsq);
+    std::swap(c->t_alloc, a.t_alloc); std::swap(c->v_alloc, a.v_alloc);
+    c->res = resolution; c->nvox = c->h_build[0]; c->cap = tcap; c->linearized = false;
+    return VIL_OK;
+}
+
 extern "C" {
 
 int vgicp_covariances(vgicp_ctx* c, int32_t n, const float* xyz, int32_t k, double* out) {
@@ -375,6 +557,7 @@ int vgicp_create(int32_t device, vgicp_ctx** out) {
     vgicp_ctx* c = new vgicp_ctx();
     hipError_t err = c->open(device, 8 * 32);
     if (err == hipSuccess) err = c->pin(&c->h_out, 8 * 32);
+    if (err == hipSuccess) err = c->pin(&c->h_build, 16);
     if (err != hipSuccess) { c->close(c->prof); delete c; VILCHK(err); }
     c->d_out = (double*)c->d_mem;
     *out = c;
@@ -383,7 +566,8 @@ int vgicp_create(int32_t device, vgicp_ctx** out) {
 void vgicp_destroy(vgicp_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    free_target(c); free_source(c);
+    free_target(c); free_source(c); free_aside(c);
+    hipFree(c->d_bws); hipFree(c->d_txyz); hipFree(c->d_tcov); c->bprof.destroy();
     hipFree(c->d_cvox); hipFree(c->d_cM); hipFree(c->d_cvox2); hipFree(c->d_cM2); hipFree(c->d_part);
     hipFree(c->gb.ws); hipFree(c->d_nn);
     if (c->d_coop) hipFree(c->d_coop); if (c->h_aout) hipHostFree(c->h_aout); if (c->h_lin) hipHostFree(c->h_lin);
@@ -399,6 +583,18 @@ void vgicp_default_options(vgicp_options* o) {
 int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* cov9_in, double resolution) {
     if (!c || n <= 0 || !xyz || !(resolution > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
+    if (c->builder == VGICP_BUILD_DEVICE) {               // points (and given covariances) up, everything else on the device
+        if ((size_t)n > c->tpts_cap) {
+            hipFree(c->d_txyz); hipFree(c->d_tcov); c->d_txyz = nullptr; c->d_tcov = nullptr; c->tpts_cap = 0;
+            const size_t cap = (size_t)n + (size_t)n / 2;
+            VILCHK(hipMalloc(&c->d_txyz, 12 * cap)); VILCHK(hipMalloc(&c->d_tcov, 72 * cap));
+            c->tpts_cap = cap;
+        }
+        VILCHK(hipMemcpyAsync(c->d_txyz, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        if (cov9_in) VILCHK(hipMemcpyAsync(c->d_tcov, cov9_in, 72 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        else { const int st = covariances_dev(c, n, c->d_txyz, KNN_MAX, c->d_tcov); if (st != VIL_OK) return st; }
+        return build_target_dev(c, n, c->d_txyz, c->d_tcov, resolution);
+    }
     std::vector<double> own;
     const double* cov9 = cov9_in;
     if (!cov9) { own.resize(9 * (size_t)n); const int st = vgicp_covariances(c, n, xyz, KNN_MAX, own.data()); if (st != VIL_OK) return st; cov9 = own.data(); }
@@ -430,7 +626,50 @@ int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* co
     { std::vector<double> wsq((size_t)nv); for (int v = 0; v < nv; ++v) wsq[v] = std::sqrt((double)num[v]); VILCHK(hipMalloc(&c->d_wsq, 8 * (size_t)nv)); VILCHK(hipMemcpy(c->d_wsq, wsq.data(), 8 * (size_t)nv, hipMemcpyHostToDevice)); }
     VILCHK(hipMemcpy(c->d_num, num.data(), 4 * (size_t)nv, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(c->d_mean, mean.data(), 8 * 3 * (size_t)nv, hipMemcpyHostToDevice));
     VILCHK(hipMemcpy(c->d_cov, cov.data(), 8 * 9 * (size_t)nv, hipMemcpyHostToDevice));
-    c->res = resolution; c->nvox = nv; c->cap = cap; c->linearized = false;
+    c->res = resolution; c->nvox = nv; c->cap = cap; c->linearized = false; c->t_alloc = cap; c->v_alloc = nv;
+    return VIL_OK;
+}
+
+int vgicp_set_voxel_builder(vgicp_ctx* c, int32_t builder) {
+    if (!c || (builder != VGICP_BUILD_HOST && builder != VGICP_BUILD_DEVICE)) return VIL_ERR_INVALID_ARGUMENT;
+    c->builder = builder;
+    return VIL_OK;
+}
+
+int vgicp_promote_source(vgicp_ctx* c, double resolution) {
+    if (!c || !c->n || !(resolution > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
+    return build_target_dev(c, c->n, c->d_sxyz, c->d_scov, resolution);
+}
+
+// voxel order from the table: the slot of a key holds the voxel's number, whichever builder made the table
+int vgicp_read_voxels(vgicp_ctx* c, vgicp_voxels* out) {
+    if (!c || !out) return VIL_ERR_INVALID_ARGUMENT;
+    const int nv = c->nvox;
+    out->count = nv;
+    if (out->capacity < nv) return VIL_ERR_INVALID_ARGUMENT;
+    if (!nv) return VIL_OK;
+    VILCHK(hipSetDevice(c->device));
+    if (out->keys) {
+        std::vector<long long> tkeys((size_t)c->cap); std::vector<int> tslot((size_t)c->cap);
+        VILCHK(hipMemcpy(tkeys.data(), c->d_keys, 8 * (size_t)c->cap, hipMemcpyDeviceToHost)); VILCHK(hipMemcpy(tslot.data(), c->d_slot, 4 * (size_t)c->cap, hipMemcpyDeviceToHost));
+        for (int h = 0; h < c->cap; ++h) if (tkeys[h] >= 0 && tslot[h] >= 0 && tslot[h] < nv) out->keys[tslot[h]] = (int64_t)tkeys[h];
+    }
+    if (out->num) VILCHK(hipMemcpy(out->num, c->d_num, 4 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->mean3) VILCHK(hipMemcpy(out->mean3, c->d_mean, 8 * 3 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->cov9) VILCHK(hipMemcpy(out->cov9, c->d_cov, 8 * 9 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->wsq) VILCHK(hipMemcpy(out->wsq, c->d_wsq, 8 * (size_t)nv, hipMemcpyDeviceToHost));
+    return VIL_OK;
+}
+
+int vgicp_build_profile_enable(vgicp_ctx* c, int32_t enable) {
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(c->bprof.enable(c->device, enable != 0));
+    return VIL_OK;
+}
+int vgicp_build_profile_read(vgicp_ctx* c, int64_t* launches, double* total_ms) {
+    if (!c || !launches || !total_ms) return VIL_ERR_INVALID_ARGUMENT;
+    c->bprof.read(launches, total_ms);
     return VIL_OK;
 }
 

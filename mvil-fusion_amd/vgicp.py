@@ -29,6 +29,16 @@ class VgicpError(RowError):
 
 _dp, _fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
 
+BUILD_HOST, BUILD_DEVICE = 0, 1
+BUILD_KERNELS = ("k_vox_clear", "k_vox_insert", "k_vox_offsets", "k_vox_fill", "k_vox_scan", "k_vox_rank", "k_vox_sum")       # VGICP_BUILD_KERNELS, in launch order
+ERR_INVALID_ARGUMENT, ERR_NON_FINITE = -1, -3
+
+
+class VgicpVoxels(C.Structure):
+    """vgicp_voxels (include/vilvgicp_voxel.h)"""
+    _fields_ = [("capacity", C.c_int32), ("count", C.c_int32), ("keys", C.POINTER(C.c_int64)), ("num", C.POINTER(C.c_int32)),
+                ("mean3", _dp), ("cov9", _dp), ("wsq", _dp)]
+
 
 class Vgicp(RowHandle):
     ERROR, KERNELS = VgicpError, ("k_vgicp_lin",)
@@ -87,6 +97,40 @@ class Vgicp(RowHandle):
         T = np.empty((4, 4)); s = VgicpSummary()
         self._chk("align", self._f("align")(self.ctx, C.c_void_p(guess.ctypes.data), C.byref(opts), C.c_void_p(T.ctypes.data), C.byref(s)))
         return T, s
+
+    # ---- the target voxel map (include/vilvgicp_voxel.h) ----
+    def set_voxel_builder(self, builder):
+        """BUILD_HOST (default) or BUILD_DEVICE; takes effect at the next set_target, also inside LoopVerify.verify(self, ...)."""
+        self._call("set_voxel_builder", C.c_int32(builder))
+
+    def promote_source(self, resolution=0.5):
+        """The resident source becomes the target, on the device; the source stays."""
+        self._call("promote_source", C.c_double(resolution))
+
+    def read_voxels(self, capacity=None):
+        """The target map in voxel order: dict of keys int64 (nv), num int32 (nv), mean float64 (nv, 3), cov (nv, 9), wsq (nv).
+        capacity: the size of the arrays handed to the library (default: the count, asked for first)."""
+        v = VgicpVoxels()
+        if capacity is None:
+            v.capacity = 1 << 30                # no array given: only the count is set
+            self._call("read_voxels", C.byref(v))
+            capacity = v.count
+        out = dict(keys=np.zeros(capacity, np.int64), num=np.zeros(capacity, np.int32), mean=np.zeros((capacity, 3)), cov=np.zeros((capacity, 9)), wsq=np.zeros(capacity))
+        v = VgicpVoxels(capacity, 0, out["keys"].ctypes.data_as(C.POINTER(C.c_int64)), out["num"].ctypes.data_as(C.POINTER(C.c_int32)),
+                        out["mean"].ctypes.data_as(_dp), out["cov"].ctypes.data_as(_dp), out["wsq"].ctypes.data_as(_dp))
+        st = self._f("read_voxels")(self.ctx, C.byref(v))
+        self.voxel_count = v.count              # set by the library even when it refuses the capacity
+        self._chk("read_voxels", st)
+        return {k: a[:v.count] for k, a in out.items()}
+
+    def build_profile_enable(self, on=True):
+        self._call("build_profile_enable", C.c_int32(1 if on else 0))
+
+    def build_profile_read(self):
+        """{kernel: (launches, total ms)} of the device builder since the last read."""
+        n = (C.c_int64 * len(BUILD_KERNELS))(); ms = (C.c_double * len(BUILD_KERNELS))()
+        self._call("build_profile_read", n, ms)
+        return {k: (int(n[i]), float(ms[i])) for i, k in enumerate(BUILD_KERNELS)}
 
 
 # ---- synthetic scan pair: a 16-ring spinning LiDAR in the 20 x 20 x 5 m room of synth.py, two poses -------------------------
