@@ -16,7 +16,8 @@
  *                    update is right-multiplicative (q (x) dq, pose_local_parameterization.cpp) where the reference uses
  *                    ceres::EigenQuaternionParameterization here; both minimise the same cost, the four capped trust-region
  *                    iterations may land on slightly different iterates.
- * The neighbour searches are EXACT (same float distances as pcl's kd-tree; ties may order differently).
+ * The neighbour searches are EXACT (same float distances as pcl's kd-tree, (dx dx + dy dy) + dz dz with every operation rounded and never fused;
+ * ties may order differently): tests/test_gpu_map_floor.py holds this on queries whose neighbours change with the last bit of a distance.
  * Points are float [x y z intensity] (PointXYZI).  Plain C, POD only, host pointers. */
 #ifndef VILMAP_H
 #define VILMAP_H

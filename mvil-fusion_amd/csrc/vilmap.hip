@@ -128,8 +128,10 @@ __global__ __launch_bounds__(64 * VM_QPB) void k_map_search(int nqc, int nqs, co
     if (nmap >= kk) {
         float sx, sy, sz;
         to_map(T, scan + 4 * (size_t)qi, sx, sy, sz);
-        const bool ok = surf ? knn_wave_query(best, sx, sy, sz, 10, nsm, Gs, os, xs, wl_all + wave * KNN_WL_CAP, 1.0f, 5)
-                             : knn_wave_query(best, sx, sy, sz, 5, ncm, Gc, oc, xc, wl_all + wave * KNN_WL_CAP, 1.0f, 5);
+        // STRICT: the header promises pcl's float distances, and the back end does fuse sqdist_nofma's sum (tests/test_gpu_map_floor.py has
+        // queries whose five neighbours change with it)
+        const bool ok = surf ? knn_wave_query<true>(best, sx, sy, sz, 10, nsm, Gs, os, xs, wl_all + wave * KNN_WL_CAP, 1.0f, 5)
+                             : knn_wave_query<true>(best, sx, sy, sz, 5, ncm, Gc, oc, xc, wl_all + wave * KNN_WL_CAP, 1.0f, 5);
         if (ok) d5 = knn_key_d(readlane_u64(best, 4));
     }
     if (lane < 10) {

@@ -1,5 +1,8 @@
-// ORACLE -- TEST INFRASTRUCTURE ONLY (never linked into or called by the product path).  PARITY UNPINNED: the
-// reference ships no tests or golden vectors for lidar_mapping and cannot be built here (Eigen / Ceres / PCL / ROS absent).
+// ORACLE -- TEST INFRASTRUCTURE ONLY (never linked into or called by the product path).  The reference ships no tests or golden
+// vectors for lidar_mapping and cannot be built here (Eigen / Ceres / PCL / ROS absent).  PINNED BY tests/test_mapreg_ref.py: the association
+// (orc_vmap_associate) against tests/mapreg_ref.py, a restatement from the reference's text with other algorithms (exhaustive numpy search, mpmath.eigsy
+// and a 50-digit least squares) -- the same accepted points wherever a gate is decided, a, b, n, d within 16 x the float64 floor -- on fixtures at the
+// gates' edges; what colPivHouseholderQr does with a rank-deficient P is NOT pinned (Eigen's pivot threshold is unknown here).
 //
 // CPU restatement of the scan-to-map registration of lidar_mapping/src/localMapping.cpp:590-791:
 //   pointAssociateToMap :170-179 ; corner points: 5 nearest map points, PCA line test :613-660 -> LidarEdgeFactor(cp, a, b, 1.0)
