@@ -47,7 +47,9 @@ typedef struct vgicp_summary {
 int vgicp_create(int32_t device, vgicp_ctx** out);
 void vgicp_destroy(vgicp_ctx* ctx);
 void vgicp_default_options(vgicp_options* o);
-/* target cloud + covariances -> Gaussian voxel map of edge `resolution` (estimator.cpp:271 uses 0.5) */
+/* target cloud + covariances -> Gaussian voxel map of edge `resolution` (estimator.cpp:271 uses 0.5).  Both builders (vilvgicp_voxel.h)
+ * build the map aside and install it when it is complete: after any failure -- VIL_ERR_NON_FINITE, or VIL_ERR_DEVICE for a failed
+ * allocation or copy -- the previous target stays usable and unchanged. */
 int vgicp_set_target(vgicp_ctx* ctx, int32_t n, const float* xyz, const double* cov9, double resolution);
 int vgicp_set_source(vgicp_ctx* ctx, int32_t n, const float* xyz, const double* cov9);
 /* Covariance of the k nearest neighbours of every point (the point itself included, as pcl's nearestKSearch returns it),

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <memory>
 #include <vector>
+#include "vil_host.hpp"
 #include "vil_internal.h"
 
 // Owned segments of the per-iteration message [camera part | h_ll, b_l, 1/pivot, scale (L each) | e_A (13 L) | e_O (6 F)]: a landmark's entries are
@@ -47,17 +48,12 @@ struct __attribute__((visibility("hidden"))) Comm {
     static int join_local(Comm** ranks, const int* devices, int n);
     void release(int device);      // THE teardown: transport, peer handles, inbox, every staging buffer
 private:
-    struct Stage {                         // grow-only staging buffer (doubles) on the device
-        double* d = nullptr; size_t cap = 0;
-        void release() { if (d) hipFree(d); d = nullptr; cap = 0; }
-        bool grow(size_t n) { if (n <= cap) return true; release(); if (hipMalloc(&d, 8 * n) != hipSuccess) { d = nullptr; return false; } cap = n; return true; }
-    };
     int alloc_agree();
     int ipc_sum(hipStream_t stream, const double* send, double* recv, size_t cnt, int sym, const OwnSeg& seg);
     int slim_sum(hipStream_t stream, const double* send, double* recv, int D, size_t span);
     ncclComm* rccl = nullptr;              // RCCL communicator over xGMI (vil_comm_init)
     std::shared_ptr<LocalComm> local;      // in-process communicator (vil_comm_init_local)
     std::shared_ptr<IpcComm> ipc;          // multi-process peer-buffer exchange (vil_comm_ipc_export / vil_comm_ipc_init)
-    Stage tmp, slim_buf;                   // result of an in-place in-process sum; staging of the packed per-iteration message
+    vilhost::Grown<double> tmp, slim_buf;  // result of an in-place in-process sum; staging of the packed per-iteration message
     double* agree_h = nullptr; double* agree_d = nullptr;      // agree(): 64 doubles each, pinned / device (RCCL and peer buffers)
 };

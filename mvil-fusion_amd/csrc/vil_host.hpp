@@ -1,12 +1,18 @@
 // vil_host.hpp -- the host scaffold shared by the row libraries (vilmap.hip, vilvgicp.hip, vilpreint.hip, vilscan.hip, vildepth.hip,
-// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers and the kernel-event profilers.
-// Header-only, internal linkage: libvilsolve.so exports nothing from here.
+// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip; through vil_voxmap.hpp, vil_knn.hpp and
+// vil_comm.hpp also their headers): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers, the kernel-event profilers,
+// the grow-only buffer (Grown), the mapped pinned record (Mapped) and the poll of a word in it (await_word).
+// Header-only, internal linkage or hidden: libvilsolve.so exports nothing from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/vilsolve.h"
@@ -15,7 +21,57 @@
 #define VILCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (getenv("VIL_DEBUG")) fprintf(stderr, "%s:%d: %s\n", __FILE_NAME__, __LINE__, hipGetErrorString(e_)); return VIL_ERR_DEVICE; } } while (0)
 
 namespace vilhost {
+
+// A grow-only buffer of T on the device (PINNED, Grown<T, true>: in pinned host memory): the one owner of everything a row allocates on demand.
+// reserve(n, alloc) does nothing while n elements fit; otherwise it releases the buffer and allocates alloc >= n elements -- the head
+// room is the call site's -- WITHOUT keeping the contents, and is left empty when that fails.  Move-only; frees in its destructor.
+template <class T, bool PINNED = false>
+struct __attribute__((visibility("hidden"))) Grown {
+    T* p = nullptr; size_t cap = 0;                         // cap: elements
+    Grown() = default;
+    Grown(Grown&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    Grown& operator=(Grown&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }      // (what this held goes with o)
+    ~Grown() { release(); }
+    hipError_t reserve(size_t n, size_t alloc) {
+        if (n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = PINNED ? hipHostMalloc((void**)&p, alloc * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, alloc * sizeof(T));
+        if (e == hipSuccess) cap = alloc; else p = nullptr;
+        return e;
+    }
+    void release() { if (p) { if (PINNED) hipHostFree(p); else hipFree(p); } p = nullptr; cap = 0; }
+};
+
+// A zeroed record in pinned host memory that a kernel writes through the device's own pointer to it (a result and the word that
+// await_word polls): open() gives both pointers or neither.
+struct __attribute__((visibility("hidden"))) Mapped {
+    char* h = nullptr; void* d = nullptr;
+    Mapped() = default;
+    Mapped(const Mapped&) = delete; Mapped& operator=(const Mapped&) = delete;
+    ~Mapped() { release(); }
+    hipError_t open(size_t bytes) {
+        release();
+        hipError_t e = hipHostMalloc((void**)&h, bytes, hipHostMallocMapped);
+        if (e != hipSuccess) { h = nullptr; return e; }
+        memset(h, 0, bytes);
+        if ((e = hipHostGetDevicePointer(&d, h, 0)) != hipSuccess) release();
+        return e;
+    }
+    void release() { if (h) hipHostFree(h); h = nullptr; d = nullptr; }
+};
+
 namespace {
+
+// Spin on a word in pinned memory that a kernel stores last, with system scope; the clock is looked at every 4096 spins.  True: the word
+// was seen and what the kernel wrote before it is visible (acquire).  False after limit_ms: the caller falls back to
+// hipStreamSynchronize, which surfaces a fault and waits for a device that is merely slow.
+inline bool await_word(volatile int* w, int want, int limit_ms) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (long spin = 1;; ++spin) {
+        if (*w == want) { std::atomic_thread_fence(std::memory_order_acquire); return true; }
+        if ((spin & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(limit_ms)) return false;
+    }
+}
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -91,6 +147,8 @@ inline bool has_device(int dev) {                          // no CPU fallback
 
 // what a row's context owns on its device: the stream, one arena of device memory (none when arena_bytes is 0) and up to four
 // pinned host buffers.  The contexts derive from it.  open() and pin() return the HIP error for the row's VILCHK.
+// Teardown is close(), which selects the device, then delete: a context's Grown and Mapped members free in their destructors, after
+// close(), with the context's device still current.  close() has destroyed the stream by then, which hipFree / hipHostFree do not need.
 struct Device {
     int device = -1;                                        // -1: never opened, close() has nothing to free
     hipStream_t stream = nullptr;

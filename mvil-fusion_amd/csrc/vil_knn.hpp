@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "vil_host.hpp"
+
 namespace vknn {
 
 __host__ __device__ inline long long pack_key(int x, int y, int z) { return ((long long)(x & 0x1FFFFF) << 42) | ((long long)(y & 0x1FFFFF) << 21) | (long long)(z & 0x1FFFFF); }
@@ -192,19 +194,13 @@ __device__ __forceinline__ bool knn_wave_query(unsigned long long& best, float q
 }
 
 // host: device work space + launches that build the grid of a device-resident cloud (stride floats per point)
-struct GridBuild { char* ws = nullptr; size_t ws_bytes = 0; GridTab G; int* order = nullptr; float* cxyz = nullptr; int n = 0; };
+struct GridBuild { vilhost::Grown<char> ws; GridTab G; int* order = nullptr; float* cxyz = nullptr; int n = 0; };      // ws: owned, freed with the context
 inline hipError_t grid_build(GridBuild& gb, int n, const float* d_xyz, int stride, float h, hipStream_t stream) {
     int cap = 1024; while (cap < 2 * n) cap <<= 1;
     const size_t bytes = 8 * (size_t)cap + 3 * 4 * (size_t)cap + 2 * 4 * (size_t)n + 12 * (size_t)n + 512;
-    if (bytes > gb.ws_bytes) {
-        if (gb.ws) { hipFree(gb.ws); gb.ws = nullptr; gb.ws_bytes = 0; }
-        const size_t want = bytes + bytes / 2;                              // head room: the next scans' maps are about this size
-        hipError_t e = hipMalloc(&gb.ws, want);
-        if (e != hipSuccess) return e;
-        gb.ws_bytes = want;
-    }
+    if (const hipError_t e = gb.ws.reserve(bytes, bytes + bytes / 2); e != hipSuccess) return e;      // head room: the next scans' maps are about this size
     GridTab& G = gb.G;
-    G.keys = (long long*)gb.ws; G.cnt = (int*)(gb.ws + 8 * (size_t)cap); G.start = G.cnt + cap; G.cur = G.start + cap; G.mask = cap - 1; G.h = h;
+    G.keys = (long long*)gb.ws.p; G.cnt = (int*)(gb.ws.p + 8 * (size_t)cap); G.start = G.cnt + cap; G.cur = G.start + cap; G.mask = cap - 1; G.h = h;
     G.nocc = G.cur + cap;
     int* pslot = G.nocc + 64; gb.order = pslot + n; gb.cxyz = (float*)(gb.order + n); gb.n = n;
     hipMemsetAsync(G.keys, 0xFF, 8 * (size_t)cap, stream);                  // every key = -1 (empty)

@@ -229,16 +229,16 @@ int Comm::slim_sum(hipStream_t stream, const double* send, double* recv, int D, 
     LocalComm* lc = rccl ? nullptr : local.get();
     int st = VIL_OK;
     if (need > slim_buf.cap) {
-        if (!slim_buf.grow(need) || hipMemsetAsync(slim_buf.d, 0, 8 * need, stream) != hipSuccess) st = VIL_ERR_DEVICE;
+        if (slim_buf.reserve(need, need) != hipSuccess || hipMemsetAsync(slim_buf.p, 0, 8 * need, stream) != hipSuccess) st = VIL_ERR_DEVICE;
         if (st != VIL_OK && !lc) return st;          // (in-process ranks carry a failure to the agreement point below)
     }
-    double* M = slim_buf.d; double* G = M + Y.camS; double* Msum = G + Y.gmax; double* Gall = Msum + Y.camS;
+    double* M = slim_buf.p; double* G = M + Y.camS; double* Msum = G + Y.gmax; double* Gall = Msum + Y.camS;
     const unsigned nb = (unsigned)std::min<size_t>(256, (Y.span + 255) / 256);
     if (st == VIL_OK) hipLaunchKernelGGL(k_slim_pack, dim3(nb), dim3(256), 0, stream, send, M, G, Y);
     if (!lc) {
         if (g_rccl.AllReduce(M, Msum, Y.camS, ncclDouble, ncclSum, rccl, stream) != ncclSuccess) return VIL_ERR_COMM;
         if (g_rccl.AllGather(G, Gall, Y.gmax, ncclDouble, rccl, stream) != ncclSuccess) return VIL_ERR_COMM;
-    } else if ((st = local_exchange(lc, rank, stream, slim_buf.d, st, [&](const PeerPtrs& pp) {      // every rank's M and G, published as one staging buffer
+    } else if ((st = local_exchange(lc, rank, stream, slim_buf.p, st, [&](const PeerPtrs& pp) {      // every rank's M and G, published as one staging buffer
         hipLaunchKernelGGL(k_slim_emul, dim3(nb), dim3(256), 0, stream, Msum, Gall, pp, Y); })) != VIL_OK) return st;
     hipLaunchKernelGGL(k_slim_unpack, dim3(nb), dim3(256), 0, stream, recv, (const double*)Msum, (const double*)Gall, Y);
     return VIL_OK;
@@ -250,12 +250,12 @@ int Comm::sum(hipStream_t stream, const double* send, double* recv, size_t cnt, 
     if (rccl) return g_rccl.AllReduce(send, recv, cnt, ncclDouble, ncclSum, rccl, stream) == ncclSuccess ? VIL_OK : VIL_ERR_COMM;
     if (local) {
         const bool inplace = send == recv;
-        int st = inplace && !tmp.grow(cnt) ? VIL_ERR_DEVICE : VIL_OK;
-        double* out = inplace ? tmp.d : recv;
+        int st = inplace && tmp.reserve(cnt, cnt) != hipSuccess ? VIL_ERR_DEVICE : VIL_OK;
+        double* out = inplace ? tmp.p : recv;
         st = local_exchange(local.get(), rank, stream, send, st, [&](const PeerPtrs& pp) {
             hipLaunchKernelGGL(k_sum_peers, dim3((unsigned)std::min<size_t>(256, (cnt + 255) / 256)), dim3(256), 0, stream, out, pp, cnt, sym, seg); });
         if (st != VIL_OK) return st;
-        if (inplace) HIPCHK(hipMemcpyAsync(recv, tmp.d, 8 * cnt, hipMemcpyDeviceToDevice, stream));
+        if (inplace) HIPCHK(hipMemcpyAsync(recv, tmp.p, 8 * cnt, hipMemcpyDeviceToDevice, stream));
         return VIL_OK;
     }
     if (send != recv) HIPCHK(hipMemcpyAsync(recv, send, 8 * cnt, hipMemcpyDeviceToDevice, stream));     // a single rank (vil_debug_set_split)

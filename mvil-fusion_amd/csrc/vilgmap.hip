@@ -426,7 +426,6 @@ int vgmap_create(int32_t device, const vgmap_config* g, vgmap_ctx** out) {
 
 void vgmap_destroy(vgmap_ctx* c) {
     if (!c) return;
-    if (c->device >= 0) { hipSetDevice(c->device); hipFree(c->gb.ws); }
     c->close(c->prof);
     delete c;
 }

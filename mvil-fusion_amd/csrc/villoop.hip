@@ -184,7 +184,6 @@ int vloop_create(int32_t device, int32_t max_points, vloop_ctx** out) {
 
 void vloop_destroy(vloop_ctx* c) {
     if (!c) return;
-    if (c->device >= 0) { hipSetDevice(c->device); hipFree(c->gb.ws); }
     c->close(c->prof);
     delete c;
 }

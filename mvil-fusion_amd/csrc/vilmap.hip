@@ -8,7 +8,6 @@
 // and the 7-parameter solve is vil_solve on a one-pose window that holds exactly these factors (k_sweep's LiDAR roles).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -248,19 +247,18 @@ void quat_to_R(const double* q, double* R) {
 
 }  // namespace
 
-struct vmap_ctx : vilhost::Device {                  // its buffers grow on demand: no arena
+struct __attribute__((visibility("hidden"))) vmap_ctx : vilhost::Device {                  // its buffers grow on demand: no arena; every member frees itself (vil_host.hpp)
     int nc = 0, ns = 0;
-    float* d_cmap = nullptr; float* d_smap = nullptr; size_t cmap_cap = 0, smap_cap = 0;
+    vilhost::Grown<float> d_cmap, d_smap;
     vknn::GridBuild gc, gs;
     float hc = 1.0f, hs = 1.0f;                      // cell sizes, adapted to the maps' densities
     // scan staging: corner points then surf points
-    float* d_scan = nullptr; size_t scan_cap = 0; float* h_scan = nullptr; size_t h_scan_cap = 0; char* d_work = nullptr; size_t work_cap = 0;
-    const float* up_corner = nullptr; const float* up_surf = nullptr; int up_nc = -1, up_ns = -1; bool scan_valid = false;
-    double* h_slot = nullptr; size_t h_slot_cap = 0;       // pinned: the slot read-back is a plain DMA
-    double* d_soa = nullptr; size_t soa_cap = 0; int* d_cnt = nullptr; int* h_cnt = nullptr;   // device-resident factor tables of vmap_align
-    vp1::Pose1Coop* d_coop = nullptr; int reg_epoch = 0;   // meeting point of the pose solve's workgroups; epoch numbers are never reused
-    char* d_reg = nullptr; char* h_reg = nullptr;     // single-submission registration: pose (7 doubles) | PoseRT | 2 x Pose1Out, and its pinned mirror
-    char* h_res = nullptr; void* d_res = nullptr;     // pinned + mapped: the second round's Pose1Out | sequence word, written by k_pose_solve, polled by the host
+    vilhost::Grown<float> d_scan; vilhost::Grown<float, true> h_scan; vilhost::Grown<char> d_work;      // d_work: ScanWork below
+    vilhost::Grown<double, true> h_slot;               // pinned: the slot read-back is a plain DMA
+    vilhost::Grown<double> d_soa; vilhost::Grown<int> d_cnt; vilhost::Grown<int, true> h_cnt;      // device-resident factor tables of vmap_align and their two counts
+    vilhost::Grown<vp1::Pose1Coop> d_coop; int reg_epoch = 0;   // meeting point of the pose solve's workgroups; epoch numbers are never reused
+    vilhost::Grown<char> d_reg; vilhost::Grown<char, true> h_reg;      // single-submission registration: pose (7 doubles) | PoseRT | 2 x Pose1Out, and its pinned mirror
+    vilhost::Mapped res;                               // the second round's Pose1Out | sequence word, written by k_pose_solve, polled by the host
     int coop_cap = -1;                                 // workgroups of k_pose_solve the device holds at once (vil_coop.hpp)
     int fused_max = 1 << 20;                           // scans up to this many points take the one-launch pose solve (vmap_set_fused_max; 0 = always the window solver)
     vilhost::Profiler<2, 4> prof;                      // k_map_search, k_map_fit
@@ -268,67 +266,98 @@ struct vmap_ctx : vilhost::Device {                  // its buffers grow on dema
 
 namespace {
 #define VM_OCC 6.0              // points per occupied grid cell the cell sizes are steered to
+
+// what d_work holds for a scan of nq points: the fit's slots (10 doubles each), the ten neighbours, the fifth distance, the ten
+// intensities, and the accepted corner / surf slots per workgroup of k_map_fit
+struct ScanWork {
+    double* slot; int* nn; float* nd5; float* nint; int* blk;
+    ScanWork(char* w, size_t nq) : slot((double*)w), nn((int*)(w + 80 * nq)), nd5((float*)(nn + 10 * nq)), nint(nd5 + nq), blk((int*)(w + ((164 * nq + 7) & ~(size_t)7))) {}
+    static size_t bytes(size_t nq) { return nq * (80 + 40 + 4 + 40) + 8 * (nq / VM_THREADS + 1) + 256; }
+};
+struct Tables { double* edge; int es; double* plane; int ps; };      // the solver's factor tables in d_soa (vil_internal.h)
+
+// a device buffer and its pinned mirror of n elements: both or neither
+template <class T>
+hipError_t reserve_pair(vilhost::Grown<T>& d, vilhost::Grown<T, true>& h, size_t n) {
+    hipError_t e = d.reserve(n, n);
+    if (e == hipSuccess && (e = h.reserve(n, n)) != hipSuccess) d.release();
+    return e;
+}
+
 int upload_scan(vmap_ctx* c, int n_corner, const float* corner, int n_surf, const float* surf) {
     const int nq = n_corner + n_surf;
-    const size_t need_scan = 16 * (size_t)nq + 16, need_work = (size_t)nq * (40 + 4 + 80 + 40) + 8 * ((size_t)nq / VM_THREADS + 1) + 256;
-    if (need_scan > c->scan_cap) { hipFree(c->d_scan); c->d_scan = nullptr; c->scan_cap = 0; VILCHK(hipMalloc(&c->d_scan, 2 * need_scan)); c->scan_cap = 2 * need_scan; }
-    if (need_work > c->work_cap) { hipFree(c->d_work); c->d_work = nullptr; c->work_cap = 0; VILCHK(hipMalloc(&c->d_work, 2 * need_work)); c->work_cap = 2 * need_work; }
+    const size_t need_scan = 4 * (size_t)nq + 4, need_work = ScanWork::bytes((size_t)nq);      // (floats, bytes)
+    VILCHK(c->d_scan.reserve(need_scan, 2 * need_scan));
+    VILCHK(c->d_work.reserve(need_work, 2 * need_work));
     // through a pinned image: one DMA instead of two staged pageable copies (every entry point ends with a stream
     // synchronisation, so the image is free again when the next call starts)
-    if (need_scan > c->h_scan_cap) { if (c->h_scan) hipHostFree(c->h_scan); c->h_scan = nullptr; c->h_scan_cap = 0; VILCHK(hipHostMalloc((void**)&c->h_scan, 2 * need_scan, hipHostMallocDefault)); c->h_scan_cap = 2 * need_scan; }
-    if (n_corner) memcpy(c->h_scan, corner, 16 * (size_t)n_corner);
-    if (n_surf) memcpy(c->h_scan + 4 * (size_t)n_corner, surf, 16 * (size_t)n_surf);
-    if (nq) VILCHK(hipMemcpyAsync(c->d_scan, c->h_scan, 16 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
+    VILCHK(c->h_scan.reserve(need_scan, 2 * need_scan));
+    if (n_corner) memcpy(c->h_scan.p, corner, 16 * (size_t)n_corner);
+    if (n_surf) memcpy(c->h_scan.p + 4 * (size_t)n_corner, surf, 16 * (size_t)n_surf);
+    if (nq) VILCHK(hipMemcpyAsync(c->d_scan.p, c->h_scan.p, 16 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
     return VIL_OK;
 }
+// the factor tables for a scan of this shape and the pair of counts
+int reserve_tables(vmap_ctx* c, int n_corner, int n_surf, Tables* tb) {
+    const int es = (std::max(n_corner, 1) + 31) & ~31, ps = (std::max(n_surf, 1) + 31) & ~31;
+    const size_t need = (size_t)9 * es + (size_t)7 * ps;
+    VILCHK(c->d_soa.reserve(need, 2 * need));
+    VILCHK(reserve_pair(c->d_cnt, c->h_cnt, 4));
+    *tb = Tables{c->d_soa.p, es, c->d_soa.p + (size_t)9 * es, ps};
+    return VIL_OK;
+}
+// Enqueues the association of the uploaded scan (nq > 0) at pose T -- Tdev: at the pose the device holds there instead -- as k_map_search and
+// k_map_fit and, with tables, k_map_compact into them.  Queries are addressed in the uploaded layout (corner block, then surf block); a
+// class without a map is skipped by nmap < k.  marks (or null): the profiler's events before / after the search and before / after
+// the fit; the middle two may be one event.
+int enqueue_association(vmap_ctx* c, int n_corner, int n_surf, const PoseD& T, const PoseD* Tdev, const int* marks, const Tables* tb) {
+    const int nq = n_corner + n_surf;
+    const ScanWork w(c->d_work.p, (size_t)nq);
+    const dim3 per_point((nq + VM_THREADS - 1) / VM_THREADS);
+    if (marks) VILCHK(c->prof.mark(marks[0], c->stream));
+    hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan.p, T, Tdev, c->nc, c->gc.G, c->gc.order, c->gc.cxyz,
+                       c->ns, c->gs.G, c->gs.order, c->gs.cxyz, w.nn, w.nd5, c->d_smap.p, w.nint);
+    if (marks) VILCHK(c->prof.mark(marks[1], c->stream));
+    if (marks && marks[2] != marks[1]) VILCHK(c->prof.mark(marks[2], c->stream));
+    hipLaunchKernelGGL(k_map_fit, per_point, dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan.p, c->d_cmap.p, c->d_smap.p, w.nn, w.nd5, w.nint, w.slot, w.blk);
+    if (marks) VILCHK(c->prof.mark(marks[3], c->stream));
+    if (tb) hipLaunchKernelGGL(k_map_compact, per_point, dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, w.slot, w.blk, tb->edge, tb->es, tb->plane, tb->ps, c->d_cnt.p);
+    return VIL_OK;
+}
+PoseD pose_of(const double* q, const double* t) { PoseD T; quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2]; return T; }
+
 // association of the uploaded scan at pose (q, t); compacted on the host in scan order
 int associate_uploaded(vmap_ctx* c, int n_corner, int n_surf, const double* q, const double* t, int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
-    PoseD T; quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
     *n_edge = 0; *n_plane = 0;
     const int nqc = c->nc ? n_corner : 0, nqs = c->ns ? n_surf : 0;       // an empty map yields no factors of that class
     const int nq = n_corner + n_surf;
     if (nq == 0 || nqc + nqs == 0) return VIL_OK;
-    // queries are addressed in the uploaded layout (corner block, then surf block); a class without a map is skipped by nmap < k
-    double* d_slot = (double*)c->d_work; int* d_nn = (int*)(c->d_work + 80 * (size_t)nq); float* d_nd5 = (float*)(d_nn + 10 * (size_t)nq); float* d_nint = d_nd5 + nq; int* d_blk = (int*)(c->d_work + (((size_t)164 * nq + 7) & ~(size_t)7));
-    VILCHK(c->prof.mark(0, c->stream));
-    hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, (const PoseD*)nullptr, c->nc, c->gc.G, c->gc.order, c->gc.cxyz,
-                       c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
-    VILCHK(c->prof.mark(1, c->stream)); VILCHK(c->prof.mark(2, c->stream));
-    hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
-    VILCHK(c->prof.mark(3, c->stream));
-    if (10 * (size_t)nq > c->h_slot_cap) {
-        if (c->h_slot) hipHostFree(c->h_slot);
-        c->h_slot = nullptr; c->h_slot_cap = 0;
-        VILCHK(hipHostMalloc((void**)&c->h_slot, 8 * 20 * (size_t)nq, hipHostMallocDefault)); c->h_slot_cap = 20 * (size_t)nq;
-    }
-    VILCHK(hipMemcpyAsync(c->h_slot, d_slot, 80 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    static const int marks[4] = {0, 1, 2, 3};
+    const int st = enqueue_association(c, n_corner, n_surf, pose_of(q, t), nullptr, marks, nullptr);
+    if (st != VIL_OK) return st;
+    VILCHK(c->h_slot.reserve(10 * (size_t)nq, 20 * (size_t)nq));
+    const double* h_slot = c->h_slot.p;
+    VILCHK(hipMemcpyAsync(c->h_slot.p, ScanWork(c->d_work.p, (size_t)nq).slot, 80 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));
     c->prof.span(0, 0, 1); c->prof.span(1, 2, 3);
-    for (int i = 0; i < n_corner; ++i) if (c->h_slot[10 * (size_t)i] != 0.0) { memcpy(edge9 + 9 * (size_t)(*n_edge), &c->h_slot[10 * (size_t)i + 1], 72); ++*n_edge; }
-    for (int i = n_corner; i < nq; ++i) if (c->h_slot[10 * (size_t)i] != 0.0) { memcpy(plane7 + 7 * (size_t)(*n_plane), &c->h_slot[10 * (size_t)i + 1], 56); ++*n_plane; }
+    for (int i = 0; i < n_corner; ++i) if (h_slot[10 * (size_t)i] != 0.0) { memcpy(edge9 + 9 * (size_t)(*n_edge), &h_slot[10 * (size_t)i + 1], 72); ++*n_edge; }
+    for (int i = n_corner; i < nq; ++i) if (h_slot[10 * (size_t)i] != 0.0) { memcpy(plane7 + 7 * (size_t)(*n_plane), &h_slot[10 * (size_t)i + 1], 56); ++*n_plane; }
     VILCHK(hipGetLastError());
     return VIL_OK;
 }
 // association of the uploaded scan with the factor tables left ON THE DEVICE in the solver's layout; only the two counts come back
 int associate_device(vmap_ctx* c, int n_corner, int n_surf, const double* q, const double* t, int32_t* n_edge, int32_t* n_plane, vil_device_lidar* dl) {
-    PoseD T; quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
     *n_edge = 0; *n_plane = 0;
-    const int nq = n_corner + n_surf;
-    const int es = (std::max(n_corner, 1) + 31) & ~31, ps = (std::max(n_surf, 1) + 31) & ~31;
-    const size_t need = 8 * ((size_t)9 * es + (size_t)7 * ps);
-    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VILCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
-    if (!c->d_cnt) { VILCHK(hipMalloc(&c->d_cnt, 16)); VILCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
-    dl->edge_soa = c->d_soa; dl->edge_stride = es; dl->plane_soa = c->d_soa + (size_t)9 * es; dl->plane_stride = ps;
-    if (nq == 0) return VIL_OK;
-    double* d_slot = (double*)c->d_work; int* d_nn = (int*)(c->d_work + 80 * (size_t)nq); float* d_nd5 = (float*)(d_nn + 10 * (size_t)nq); float* d_nint = d_nd5 + nq; int* d_blk = (int*)(c->d_work + (((size_t)164 * nq + 7) & ~(size_t)7));
-    hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, (const PoseD*)nullptr, c->nc, c->gc.G, c->gc.order, c->gc.cxyz,
-                       c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
-    hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
-    hipLaunchKernelGGL(k_map_compact, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, d_slot, d_blk, c->d_soa, es, c->d_soa + (size_t)9 * es, ps, c->d_cnt);
-    VILCHK(hipMemcpyAsync(c->h_cnt, c->d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
+    Tables tb;
+    int st = reserve_tables(c, n_corner, n_surf, &tb);
+    if (st != VIL_OK) return st;
+    dl->edge_soa = tb.edge; dl->edge_stride = tb.es; dl->plane_soa = tb.plane; dl->plane_stride = tb.ps;
+    if (n_corner + n_surf == 0) return VIL_OK;
+    if ((st = enqueue_association(c, n_corner, n_surf, pose_of(q, t), nullptr, nullptr, &tb)) != VIL_OK) return st;
+    VILCHK(hipMemcpyAsync(c->h_cnt.p, c->d_cnt.p, 8, hipMemcpyDeviceToHost, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));
     VILCHK(hipGetLastError());
-    *n_edge = c->h_cnt[0]; *n_plane = c->h_cnt[1];
+    *n_edge = c->h_cnt.p[0]; *n_plane = c->h_cnt.p[1];
     return VIL_OK;
 }
 
@@ -342,65 +371,49 @@ int associate_device(vmap_ctx* c, int n_corner, int n_surf, const double* q, con
 int align_fused(vmap_ctx* c, int n_corner, int n_surf, double* q, double* t, const vil_options* opts, vmap_summary* out) {
     const auto t0 = std::chrono::steady_clock::now();
     const int nq = n_corner + n_surf;
-    const int es = (std::max(n_corner, 1) + 31) & ~31, ps = (std::max(n_surf, 1) + 31) & ~31;
-    const size_t need = 8 * ((size_t)9 * es + (size_t)7 * ps);
-    if (need > c->soa_cap) { hipFree(c->d_soa); c->d_soa = nullptr; c->soa_cap = 0; VILCHK(hipMalloc(&c->d_soa, 2 * need)); c->soa_cap = 2 * need; }
-    if (!c->d_cnt) { VILCHK(hipMalloc(&c->d_cnt, 16)); VILCHK(hipHostMalloc((void**)&c->h_cnt, 16, hipHostMallocDefault)); }
-    if (!c->d_reg) { VILCHK(hipMalloc(&c->d_reg, REG_BYTES)); VILCHK(hipHostMalloc((void**)&c->h_reg, REG_BYTES, hipHostMallocDefault)); }
-    if (!c->d_coop) { VILCHK(hipMalloc(&c->d_coop, sizeof(vp1::Pose1Coop))); VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }
-    if (!c->h_res && !getenv("VIL_NO_POLL")) {
-        if (hipHostMalloc((void**)&c->h_res, sizeof(vp1::Pose1Out) + 64, hipHostMallocMapped) == hipSuccess) {
-            memset(c->h_res, 0, sizeof(vp1::Pose1Out) + 64);
-            if (hipHostGetDevicePointer(&c->d_res, c->h_res, 0) != hipSuccess) { hipHostFree(c->h_res); c->h_res = nullptr; c->d_res = nullptr; }
-        } else c->h_res = nullptr;
+    Tables tb;
+    int st = reserve_tables(c, n_corner, n_surf, &tb);
+    if (st != VIL_OK) return st;
+    VILCHK(reserve_pair(c->d_reg, c->h_reg, REG_BYTES));
+    if (!c->d_coop.p) {                                  // zeroed flags or no meeting point at all
+        VILCHK(c->d_coop.reserve(1, 1));
+        if (hipMemsetAsync(c->d_coop.p, 0, sizeof(vp1::Pose1Coop), c->stream) != hipSuccess) { c->d_coop.release(); return VIL_ERR_DEVICE; }
     }
+    if (!c->res.h && !getenv("VIL_NO_POLL")) c->res.open(sizeof(vp1::Pose1Out) + 64);      // (without it: copy + synchronise below)
     std::unique_lock<std::shared_mutex> coop_lock(vilcoop::gate(c->device));                     // k_pose_solve's workgroups wait for one another (vil_coop.hpp)
     const int G = std::min(std::min(VP1_MAXG, c->coop_cap), std::max(1, (nq + VP1_THREADS - 1) / VP1_THREADS));
-    double* edge_soa = c->d_soa; double* plane_soa = c->d_soa + (size_t)9 * es;
-    double* h_pose = (double*)(c->h_reg + REG_POSE);
+    char* const d_reg = c->d_reg.p; char* const h_reg = c->h_reg.p;
+    double* h_pose = (double*)(h_reg + REG_POSE);
     h_pose[0] = t[0]; h_pose[1] = t[1]; h_pose[2] = t[2]; h_pose[3] = q[0]; h_pose[4] = q[1]; h_pose[5] = q[2]; h_pose[6] = q[3];
     vp1::Pose1In pin0, pin1; memset(&pin0, 0, sizeof pin0); memset(&pin1, 0, sizeof pin1);
     for (int k = 0; k < 7; ++k) pin0.pose[k] = h_pose[k];
     pin0.use = 1;                                        // the starting pose rides in the first solve's arguments (no 56-byte upload)
     int seq_expect = 0;
-    volatile int* hseq = c->h_res ? (volatile int*)(c->h_res + sizeof(vp1::Pose1Out)) : nullptr;
+    vp1::Pose1Out* const d_res = (vp1::Pose1Out*)c->res.d;
+    volatile int* hseq = c->res.h ? (volatile int*)(c->res.h + sizeof(vp1::Pose1Out)) : nullptr;
     if (hseq) *hseq = -1;
-    PoseD T; quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
-    double* d_slot = (double*)c->d_work; int* d_nn = (int*)(c->d_work + 80 * (size_t)nq); float* d_nd5 = (float*)(d_nn + 10 * (size_t)nq); float* d_nint = d_nd5 + nq; int* d_blk = (int*)(c->d_work + (((size_t)164 * nq + 7) & ~(size_t)7));
-    vp1::Pose1Out* d_out = (vp1::Pose1Out*)(c->d_reg + REG_OUT);
+    const PoseD T = pose_of(q, t);
+    vp1::Pose1Out* d_out = (vp1::Pose1Out*)(d_reg + REG_OUT);
+    static const int marks[4] = {0, 1, 1, 2};             // round 0 is the profiled one
     for (int round = 0; round < 2; ++round) {
-        if (nq > 0) {
-            if (round == 0) VILCHK(c->prof.mark(0, c->stream));
-            hipLaunchKernelGGL(k_map_search, dim3((nq + VM_QPB - 1) / VM_QPB), dim3(64 * VM_QPB), 0, c->stream, n_corner, n_surf, c->d_scan, T, round ? (const PoseD*)(c->d_reg + REG_RT) : (const PoseD*)nullptr,
-                               c->nc, c->gc.G, c->gc.order, c->gc.cxyz, c->ns, c->gs.G, c->gs.order, c->gs.cxyz, d_nn, d_nd5, c->d_smap, d_nint);
-            if (round == 0) VILCHK(c->prof.mark(1, c->stream));
-            hipLaunchKernelGGL(k_map_fit, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, c->d_scan, c->d_cmap, c->d_smap, d_nn, d_nd5, d_nint, d_slot, d_blk);
-            if (round == 0) VILCHK(c->prof.mark(2, c->stream));
-            hipLaunchKernelGGL(k_map_compact, dim3((nq + VM_THREADS - 1) / VM_THREADS), dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, d_slot, d_blk, edge_soa, es, plane_soa, ps, c->d_cnt);
-        } else VILCHK(hipMemsetAsync(c->d_cnt, 0, 8, c->stream));
-        hipLaunchKernelGGL(vp1::k_pose_solve, dim3(G), dim3(VP1_THREADS), 0, c->stream, c->d_cnt, edge_soa, es, plane_soa, ps, (double*)(c->d_reg + REG_POSE), (PoseD*)(c->d_reg + REG_RT), *opts,
-                           round ? d_out : (const vp1::Pose1Out*)nullptr, d_out + round, c->d_coop, c->reg_epoch, round ? pin1 : pin0,
-                           (round && c->d_res) ? (vp1::Pose1Out*)c->d_res : (vp1::Pose1Out*)nullptr, (round && c->d_res) ? (int*)((char*)c->d_res + sizeof(vp1::Pose1Out)) : (int*)nullptr);
+        if (nq > 0) { if ((st = enqueue_association(c, n_corner, n_surf, T, round ? (const PoseD*)(d_reg + REG_RT) : nullptr, round ? nullptr : marks, &tb)) != VIL_OK) return st; }
+        else VILCHK(hipMemsetAsync(c->d_cnt.p, 0, 8, c->stream));
+        hipLaunchKernelGGL(vp1::k_pose_solve, dim3(G), dim3(VP1_THREADS), 0, c->stream, c->d_cnt.p, tb.edge, tb.es, tb.plane, tb.ps, (double*)(d_reg + REG_POSE), (PoseD*)(d_reg + REG_RT), *opts,
+                           round ? d_out : (const vp1::Pose1Out*)nullptr, d_out + round, c->d_coop.p, c->reg_epoch, round ? pin1 : pin0,
+                           round ? d_res : (vp1::Pose1Out*)nullptr, (round && d_res) ? (int*)(d_res + 1) : (int*)nullptr);
         if (round) seq_expect = c->reg_epoch + 1;
         c->reg_epoch += std::min(std::max(opts->max_iterations, 0), VP1_MAX_ITER) + 8;     // one epoch per evaluation: at most max_iterations + 1
-        if (c->reg_epoch > (1 << 30)) { c->reg_epoch = 0; VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(vp1::Pose1Coop), c->stream)); }   // flags are compared by order: start over from zeroed flags
+        if (c->reg_epoch > (1 << 30)) { c->reg_epoch = 0; VILCHK(hipMemsetAsync(c->d_coop.p, 0, sizeof(vp1::Pose1Coop), c->stream)); }   // flags are compared by order: start over from zeroed flags
     }
-    bool polled = false;
-    if (hseq && !c->prof.on) {                         // the second solve's last act is the record + its sequence word in pinned memory
-        const auto tp0 = std::chrono::steady_clock::now();
-        for (long spin = 1;; ++spin) {
-            if (*hseq == seq_expect) { polled = true; break; }
-            if ((spin & 0xfff) == 0 && std::chrono::steady_clock::now() - tp0 > std::chrono::milliseconds(500)) break;
-        }
-        if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_reg + REG_OUT + sizeof(vp1::Pose1Out), c->h_res, sizeof(vp1::Pose1Out)); }
-    }
-    if (!polled) {
-        VILCHK(hipMemcpyAsync(c->h_reg + REG_OUT, d_out, 2 * sizeof(vp1::Pose1Out), hipMemcpyDeviceToHost, c->stream));
+    // the second solve's last act is the record + its sequence word in pinned memory
+    if (hseq && !c->prof.on && vilhost::await_word(hseq, seq_expect, 500)) memcpy(h_reg + REG_OUT + sizeof(vp1::Pose1Out), c->res.h, sizeof(vp1::Pose1Out));
+    else {
+        VILCHK(hipMemcpyAsync(h_reg + REG_OUT, d_out, 2 * sizeof(vp1::Pose1Out), hipMemcpyDeviceToHost, c->stream));
         VILCHK(hipStreamSynchronize(c->stream));
     }
     VILCHK(hipGetLastError());
     if (nq > 0) { c->prof.span(0, 0, 1); c->prof.span(1, 1, 2); }
-    const vp1::Pose1Out* r = (const vp1::Pose1Out*)(c->h_reg + REG_OUT);
+    const vp1::Pose1Out* r = (const vp1::Pose1Out*)(h_reg + REG_OUT);
     if (r[1].status != 0) return r[1].status;
     t[0] = r[1].pose[0]; t[1] = r[1].pose[1]; t[2] = r[1].pose[2]; q[0] = r[1].pose[3]; q[1] = r[1].pose[4]; q[2] = r[1].pose[5]; q[3] = r[1].pose[6];
     out->rounds = 2; out->n_edge = r[1].n_edge; out->n_plane = r[1].n_plane; out->iterations = r[1].iterations; out->initial_cost = r[1].initial_cost; out->final_cost = r[1].final_cost;
@@ -421,8 +434,6 @@ int vmap_create(int32_t device, vmap_ctx** out) {
 }
 void vmap_destroy(vmap_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipFree(c->d_cmap); hipFree(c->d_smap); hipFree(c->gc.ws); hipFree(c->gs.ws); hipFree(c->d_scan); hipFree(c->d_work); if (c->h_slot) hipHostFree(c->h_slot); hipFree(c->d_soa); hipFree(c->d_cnt); if (c->h_cnt) hipHostFree(c->h_cnt); hipFree(c->d_reg); if (c->h_reg) hipHostFree(c->h_reg); if (c->h_res) hipHostFree(c->h_res); hipFree(c->d_coop); if (c->h_scan) hipHostFree(c->h_scan);
     c->close(c->prof);
     delete c;
 }
@@ -431,12 +442,12 @@ int vmap_set_map(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const
     if (!c || nc < 0 || ns < 0 || (nc && !corner) || (ns && !surf)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     c->nc = 0; c->ns = 0;
-    if (16 * (size_t)nc > c->cmap_cap) { hipFree(c->d_cmap); c->d_cmap = nullptr; c->cmap_cap = 0; VILCHK(hipMalloc(&c->d_cmap, 24 * (size_t)nc)); c->cmap_cap = 24 * (size_t)nc; }
-    if (16 * (size_t)ns > c->smap_cap) { hipFree(c->d_smap); c->d_smap = nullptr; c->smap_cap = 0; VILCHK(hipMalloc(&c->d_smap, 24 * (size_t)ns)); c->smap_cap = 24 * (size_t)ns; }
-    if (nc) VILCHK(hipMemcpyAsync(c->d_cmap, corner, 16 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
-    if (ns) VILCHK(hipMemcpyAsync(c->d_smap, surf, 16 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
-    if (nc) VILCHK(vknn::grid_build_adaptive(c->gc, nc, c->d_cmap, 4, c->hc, VM_OCC, c->stream));
-    if (ns) VILCHK(vknn::grid_build_adaptive(c->gs, ns, c->d_smap, 4, c->hs, VM_OCC, c->stream));
+    VILCHK(c->d_cmap.reserve(4 * (size_t)nc, 6 * (size_t)nc));
+    VILCHK(c->d_smap.reserve(4 * (size_t)ns, 6 * (size_t)ns));
+    if (nc) VILCHK(hipMemcpyAsync(c->d_cmap.p, corner, 16 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
+    if (ns) VILCHK(hipMemcpyAsync(c->d_smap.p, surf, 16 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
+    if (nc) VILCHK(vknn::grid_build_adaptive(c->gc, nc, c->d_cmap.p, 4, c->hc, VM_OCC, c->stream));
+    if (ns) VILCHK(vknn::grid_build_adaptive(c->gs, ns, c->d_smap.p, 4, c->hs, VM_OCC, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));
     c->nc = nc; c->ns = ns;
     return VIL_OK;

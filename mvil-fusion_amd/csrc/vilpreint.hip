@@ -313,9 +313,9 @@ void vpre_launch_slot(hipStream_t stream, int ns, const double* dt, const double
     hipLaunchKernelGGL(k_preint, dim3(1), dim3(PRE_THREADS), 0, stream, A);
 }
 
-struct vpre_ctx : vilhost::Device {                  // both buffers grow on demand: no arena
-    char* d_buf = nullptr; size_t cap = 0;
-    char* h = nullptr; size_t hcap = 0;              // pinned staging: one H2D in, one D2H back
+struct __attribute__((visibility("hidden"))) vpre_ctx : vilhost::Device {                  // both buffers grow on demand: no arena
+    vilhost::Grown<char> d_buf;
+    vilhost::Grown<char, true> h_buf;                // pinned staging: one H2D in, one D2H back
     vilhost::Profiler<1, 2> prof;                      // k_preint
 };
 
@@ -331,8 +331,6 @@ int vpre_create(int32_t device, vpre_ctx** out) {
 }
 void vpre_destroy(vpre_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    hipFree(c->d_buf); if (c->h) hipHostFree(c->h);
     c->close(c->prof);
     delete c;
 }
@@ -353,29 +351,30 @@ int vpre_integrate(vpre_ctx* c, int32_t n, const int32_t* start, const double* d
     // one staging buffer: [start | dt | acc | gyr | acc0 | gyr0 | ba | bg] in, [out | jac] back
     const size_t o_start = 0, o_dt = (4 * (size_t)(n + 1) + 7) & ~(size_t)7, o_acc = o_dt + 8 * ns, o_gyr = o_acc + 24 * ns, o_a0 = o_gyr + 24 * ns, o_g0 = o_a0 + 24 * (size_t)n,
                  o_ba = o_g0 + 24 * (size_t)n, o_bg = o_ba + 24 * (size_t)n, in_bytes = o_bg + 24 * (size_t)n, o_out = in_bytes, o_jac = o_out + 8 * 287 * (size_t)n, total = o_jac + 8 * 225 * (size_t)n;
-    if (total > c->cap) { hipFree(c->d_buf); c->d_buf = nullptr; c->cap = 0; VILCHK(hipMalloc(&c->d_buf, 2 * total)); c->cap = 2 * total; }
-    if (total > c->hcap) { if (c->h) hipHostFree(c->h); c->h = nullptr; c->hcap = 0; VILCHK(hipHostMalloc((void**)&c->h, 2 * total, hipHostMallocDefault)); c->hcap = 2 * total; }
-    memcpy(c->h + o_start, start, 4 * (size_t)(n + 1));
-    if (ns) { memcpy(c->h + o_dt, dt, 8 * ns); memcpy(c->h + o_acc, acc, 24 * ns); memcpy(c->h + o_gyr, gyr, 24 * ns); }
-    memcpy(c->h + o_a0, acc0, 24 * (size_t)n); memcpy(c->h + o_g0, gyr0, 24 * (size_t)n); memcpy(c->h + o_ba, ba, 24 * (size_t)n); memcpy(c->h + o_bg, bg, 24 * (size_t)n);
+    VILCHK(c->d_buf.reserve(total, 2 * total));
+    VILCHK(c->h_buf.reserve(total, 2 * total));
+    char* const d = c->d_buf.p; char* const h = c->h_buf.p;
+    memcpy(h + o_start, start, 4 * (size_t)(n + 1));
+    if (ns) { memcpy(h + o_dt, dt, 8 * ns); memcpy(h + o_acc, acc, 24 * ns); memcpy(h + o_gyr, gyr, 24 * ns); }
+    memcpy(h + o_a0, acc0, 24 * (size_t)n); memcpy(h + o_g0, gyr0, 24 * (size_t)n); memcpy(h + o_ba, ba, 24 * (size_t)n); memcpy(h + o_bg, bg, 24 * (size_t)n);
     const auto t1 = now();
-    VILCHK(hipMemcpyAsync(c->d_buf, c->h, in_bytes, hipMemcpyHostToDevice, c->stream));
+    VILCHK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream));
     const auto t2 = now();
     PreArgs A;
-    A.n = n; A.start = (const int*)(c->d_buf + o_start); A.dt = (const double*)(c->d_buf + o_dt); A.acc = (const double*)(c->d_buf + o_acc); A.gyr = (const double*)(c->d_buf + o_gyr);
-    A.acc0 = (const double*)(c->d_buf + o_a0); A.gyr0 = (const double*)(c->d_buf + o_g0); A.ba = (const double*)(c->d_buf + o_ba); A.bg = (const double*)(c->d_buf + o_bg);
+    A.n = n; A.start = (const int*)(d + o_start); A.dt = (const double*)(d + o_dt); A.acc = (const double*)(d + o_acc); A.gyr = (const double*)(d + o_gyr);
+    A.acc0 = (const double*)(d + o_a0); A.gyr0 = (const double*)(d + o_g0); A.ba = (const double*)(d + o_ba); A.bg = (const double*)(d + o_bg);
     for (int q = 0; q < 4; ++q) A.nz[q] = noise4[q];
-    A.out = (double*)(c->d_buf + o_out); A.jac = jacobian ? (double*)(c->d_buf + o_jac) : nullptr;
+    A.out = (double*)(d + o_out); A.jac = jacobian ? (double*)(d + o_jac) : nullptr;
     VILCHK(c->prof.mark(0, c->stream));
     hipLaunchKernelGGL(k_preint, dim3(n), dim3(PRE_THREADS), 0, c->stream, A);
     VILCHK(c->prof.mark(1, c->stream));
-    VILCHK(hipMemcpyAsync(c->h + o_out, c->d_buf + o_out, (jacobian ? total : o_jac) - o_out, hipMemcpyDeviceToHost, c->stream));
+    VILCHK(hipMemcpyAsync(h + o_out, d + o_out, (jacobian ? total : o_jac) - o_out, hipMemcpyDeviceToHost, c->stream));
     const auto t3 = now();
     VILCHK(hipStreamSynchronize(c->stream));
     const auto t4 = now();
     VILCHK(hipGetLastError());
-    memcpy(imu_const, c->h + o_out, 8 * 287 * (size_t)n);
-    if (jacobian) memcpy(jacobian, c->h + o_jac, 8 * 225 * (size_t)n);
+    memcpy(imu_const, h + o_out, 8 * 287 * (size_t)n);
+    if (jacobian) memcpy(jacobian, h + o_jac, 8 * 225 * (size_t)n);
     if (timing) fprintf(stderr, "vpre: stage %.1f h2d %.1f launch+d2h %.1f sync %.1f copy-out %.1f us\n", us(t0, t1), us(t1, t2), us(t2, t3), us(t3, t4), us(t4, now()));
     c->prof.span(0, 0, 1);
     return VIL_OK;

@@ -19,8 +19,6 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <chrono>
 #include <unordered_map>
 #include <vector>
 
@@ -284,163 +282,54 @@ __global__ __launch_bounds__(VG_THREADS) void k_knn_fit(int n, const float* __re
 
 struct HostKeyHash { size_t operator()(long long k) const { return (size_t)hash_key(k) * 2654435761u ^ (size_t)(k >> 17); } };
 
-// ---- the target voxel map on the device (docs/voxelmap.md): GaussianVoxelMap::create_voxelmap's sequential sums, reproduced bit for bit.
-// Membership by an open-addressing table (64-bit compare-and-swap, as vknn::grid_slot); a voxel's number is the count of "first point of
-// its voxel" flags below its first point (atomicMin per slot + a prefix sum over the points); every voxel's members are put into ascending
-// index order by ranking them inside the voxel's run, and one lane per (voxel, component) then adds the run in that order from 0.0 -- the
-// host loop's additions, one by one.  Integer atomics only: which slot a key lands in and where a run lies depend on timing, no result does.
-struct VoxBuild {
-    long long* keys; int* slot_vox; int mask;             // the table being built (the set aside, not the live target)
-    int* cnt; int* cur; int* start; unsigned* first;      // per table slot: members, fill cursor, start of the run, smallest member
-    int* pslot; int* member; int* sorted; int* vstart;    // per point: its slot, the runs as filled, the runs in index order; per voxel: start of its run
-    int* bsum; int* boff;                                 // per 256 points: first-point flags in the block, and in all blocks before it
-    int* ctr;                                             // [0] run cursor, [1] voxels, [2] non-finite flag
-    int* num; double* mean; double* cov; double* wsq;     // the voxel records (SoA, voxel order)
-};
-
-__device__ __forceinline__ long long vox_key_exact(float x, float y, float z, double res) {
-#pragma clang fp contract(off)
-    const double px = (double)x, py = (double)y, pz = (double)z;          // IEEE divide, subtract, floor: the host's expression, operation by operation
-    return pack_key((int)floor(px / res - 0.5), (int)floor(py / res - 0.5), (int)floor(pz / res - 0.5));
-}
-
-// every slot of the table in use empty, the counters zero: nothing of an earlier (larger) build is read again
-__global__ __launch_bounds__(VG_THREADS) void k_vox_clear(int tcap, VoxBuild B) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < 4) B.ctr[e] = 0;
-    if (e >= tcap) return;
-    B.keys[e] = -1LL; B.slot_vox[e] = -1; B.cnt[e] = 0; B.cur[e] = 0; B.first[e] = 0xFFFFFFFFu;
-}
-__global__ __launch_bounds__(VG_THREADS) void k_vox_insert(int n, const float* __restrict__ xyz, double res, VoxBuild B) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) { B.pslot[i] = -1; atomicOr(B.ctr + 2, 1); return; }
-    const long long key = vox_key_exact(x, y, z, res);
-    int s = -1;
-    for (unsigned h = hash_key(key) & B.mask;; h = (h + 1) & B.mask) {      // at most n keys in >= 2 n slots: never full
-        long long k = B.keys[h];
-        if (k < 0) k = (long long)atomicCAS((unsigned long long*)(B.keys + h), (unsigned long long)-1LL, (unsigned long long)key);      // a stale -1 is settled here
-        if (k < 0 || k == key) { s = (int)h; break; }
-    }
-    B.pslot[i] = s;
-    atomicAdd(B.cnt + s, 1);
-    atomicMin(B.first + s, (unsigned)i);
-}
-// every occupied slot claims a contiguous run (where it lies is irrelevant, as in vknn::k_grid_offsets)
-__global__ __launch_bounds__(VG_THREADS) void k_vox_offsets(int tcap, VoxBuild B) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= tcap) return;
-    const int c = B.cnt[e];
-    if (c) B.start[e] = atomicAdd(B.ctr, c);
-}
-// members into their runs in arrival order; the block's number of first points for the numbering
-__global__ __launch_bounds__(VG_THREADS) void k_vox_fill(int n, VoxBuild B) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = i < n ? B.pslot[i] : -1;
-    if (s >= 0) B.member[B.start[s] + atomicAdd(B.cur + s, 1)] = i;
-    const int firsts = __syncthreads_count(s >= 0 && B.first[s] == (unsigned)i);
-    if (threadIdx.x == 0) B.bsum[blockIdx.x] = firsts;
-}
-// exclusive prefix sum of the block counts by one workgroup, 256 at a time with a carry; the total is the number of voxels
-__global__ __launch_bounds__(VG_THREADS) void k_vox_scan(int nb, VoxBuild B) {
-    __shared__ int wtot[VG_THREADS / 64];
-    __shared__ int carry_sh;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) carry_sh = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += VG_THREADS) {
-        const int x = base + t < nb ? B.bsum[base + t] : 0;
-        int incl = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); incl += lane >= o ? v : 0; }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wtot[w];
-        const int carry = carry_sh;
-        if (base + t < nb) B.boff[base + t] = carry + woff + incl - x;
-        __syncthreads();
-        if (t == VG_THREADS - 1) carry_sh = carry + woff + incl;
-        __syncthreads();
-    }
-    if (t == 0) B.ctr[1] = carry_sh;
-}
-// numbering: a voxel's number is the count of first points before its own; ranking: a member's place in its run is the count of smaller members
-__global__ __launch_bounds__(VG_THREADS) void k_vox_rank(int n, VoxBuild B) {
-    __shared__ int wtot[VG_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int i = blockIdx.x * blockDim.x + t;
-    const int s = i < n ? B.pslot[i] : -1;
-    const bool is_first = s >= 0 && B.first[s] == (unsigned)i;
-    const unsigned long long bal = __ballot(is_first);
-    if (lane == 0) wtot[wave] = __popcll(bal);
-    __syncthreads();
-    if (s < 0) return;
-    const int b = B.start[s], c = B.cnt[s];
-    if (is_first) {
-        int v = B.boff[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) v += wtot[w];
-        B.slot_vox[s] = v; B.vstart[v] = b; B.num[v] = c; B.wsq[v] = sqrt((double)c);
-    }
-    int r = 0;
-    for (int q = 0; q < c; ++q) r += B.member[b + q] < i ? 1 : 0;
-    B.sorted[b + r] = i;
-}
-// one lane per (voxel, component): 3 of the mean, 9 of the covariance; the run in ascending point index, starting from 0.0
-__global__ __launch_bounds__(VG_THREADS) void k_vox_sum(const float* __restrict__ xyz, const double* __restrict__ cov9, VoxBuild B) {
-#pragma clang fp contract(off)
-    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int v = (int)(tid / 12), q = (int)(tid - 12 * (long long)v);
-    if (v >= B.ctr[1]) return;
-    const int b = B.vstart[v], c = B.num[v];
-    double acc = 0.0;
-    int u = 0;
-    for (; u + 4 <= c; u += 4) {                          // the loads of four members go out together, the additions stay in order
-        const int i0 = B.sorted[b + u], i1 = B.sorted[b + u + 1], i2 = B.sorted[b + u + 2], i3 = B.sorted[b + u + 3];
-        const double a0 = q < 3 ? (double)xyz[3 * (size_t)i0 + q] : cov9[9 * (size_t)i0 + q - 3], a1 = q < 3 ? (double)xyz[3 * (size_t)i1 + q] : cov9[9 * (size_t)i1 + q - 3];
-        const double a2 = q < 3 ? (double)xyz[3 * (size_t)i2 + q] : cov9[9 * (size_t)i2 + q - 3], a3 = q < 3 ? (double)xyz[3 * (size_t)i3 + q] : cov9[9 * (size_t)i3 + q - 3];
-        acc += a0; acc += a1; acc += a2; acc += a3;
-    }
-    for (; u < c; ++u) { const int i = B.sorted[b + u]; acc += q < 3 ? (double)xyz[3 * (size_t)i + q] : cov9[9 * (size_t)i + q - 3]; }
-    const double m = acc / (double)c;                     // finalize(): the IEEE divide
-    if (q < 3) B.mean[3 * (size_t)v + q] = m; else B.cov[9 * (size_t)v + q - 3] = m;
-}
-
 }  // namespace
 
-struct vgicp_ctx : vilhost::Device {                 // d_mem is d_out; everything else grows on demand
-    // target voxel map
-    double res = 1.0; int nvox = 0, cap = 0;
-    long long* d_keys = nullptr; int* d_slot = nullptr; int* d_num = nullptr; double* d_mean = nullptr; double* d_cov = nullptr; double* d_wsq = nullptr;
+#include "vil_voxmap.hpp"      // the target voxel map: VoxSet, the k_vox_* kernels (their place among this file's kernels) and build_target_dev
+
+namespace { struct CorrCache { vilhost::Grown<int> vox; vilhost::Grown<double> M; }; }      // per slot: the voxel (-1: none) and the Mahalanobis matrix
+
+struct __attribute__((visibility("hidden"))) vgicp_ctx : vilhost::Device {                 // d_mem is d_out; everything else grows on demand and frees itself (vil_host.hpp)
+    VoxSet live, aside;                                // the target voxel map; the builders fill aside and ONE swap installs it
     // source
-    int n = 0; float* d_sxyz = nullptr; double* d_scov = nullptr;
-    // correspondences of the last linearisation
-    int noff = 1, slots = 0, slots_cap = 0; int* d_cvox = nullptr; double* d_cM = nullptr;
-    char* h_lin = nullptr; void* d_lin = nullptr; int lin_tag = 0;          // pinned + mapped: 32 doubles | tag word of vgicp_linearize / vgicp_compute_error
-    int slots_cap2 = 0; int* d_cvox2 = nullptr; double* d_cM2 = nullptr;            // second correspondence cache of k_vgicp_align (speculative linearisation)
-    double* d_part = nullptr; int part_cap = 0; double* d_out = nullptr; double* h_out = nullptr;
+    int n = 0; vilhost::Grown<float> d_sxyz; vilhost::Grown<double> d_scov;
+    // [0]: correspondences of the last linearisation; [1]: k_vgicp_align's speculative linearisation (swapped as a unit when an alignment ended there)
+    int noff = 1, slots = 0; CorrCache cache[2];
+    vilhost::Mapped lin; int lin_tag = 0;              // 32 doubles | tag word of vgicp_linearize / vgicp_compute_error
+    vilhost::Grown<double> d_part; double* d_out = nullptr; double* h_out = nullptr;
     bool linearized = false;
     vilhost::Profiler<1, 2> prof;                      // k_vgicp_lin
-    void* d_coop = nullptr; void* d_aout = nullptr; void* h_aout = nullptr; int coop_epoch = 0;       // one-launch alignment (k_vgicp_align)
+    vilhost::Grown<char> d_coop; vilhost::Mapped aout; int coop_epoch = 0;      // one-launch alignment (k_vgicp_align): VgCoop and VgAlignOut, both or neither
     // neighbour search of the covariance estimation
-    vknn::GridBuild gb; float grid_h = 1.0f; int grid_min = 4096; int coop_cap = -1; int* d_nn = nullptr; size_t nn_cap = 0;
-    // device builder of the target map (build_target_dev): everything below grows on demand and is never freed between calls
+    vknn::GridBuild gb; float grid_h = 1.0f; int grid_min = 4096; int coop_cap = -1; vilhost::Grown<int> d_nn;
+    // device builder of the target map (build_target_dev)
     int builder = VGICP_BUILD_HOST;
-    int t_alloc = 0, v_alloc = 0;                          // table slots / voxel records the live target's buffers hold
-    struct VoxSet { long long* keys = nullptr; int* slot = nullptr; int* num = nullptr; double* mean = nullptr; double* cov = nullptr; double* wsq = nullptr; int t_alloc = 0, v_alloc = 0; } aside;      // built aside, swapped in when the build succeeded
-    char* d_bws = nullptr; size_t bws_bytes = 0;          // work space of the build
-    float* d_txyz = nullptr; double* d_tcov = nullptr; size_t tpts_cap = 0;       // the target's points and covariances (vgicp_set_target, device builder)
+    vilhost::Grown<char> d_bws;                        // work space of the build
+    vilhost::Grown<float> d_txyz; vilhost::Grown<double> d_tcov;      // the target's points and covariances (vgicp_set_target, device builder)
     int* h_build = nullptr;                                // pinned: voxels | non-finite flag
     vilhost::Profiler<VGICP_BUILD_KERNELS, VGICP_BUILD_KERNELS + 1> bprof;
 };
 
-static void free_target(vgicp_ctx* c) { hipFree(c->d_keys); hipFree(c->d_slot); hipFree(c->d_num); hipFree(c->d_mean); hipFree(c->d_cov); hipFree(c->d_wsq); c->d_wsq = nullptr; c->d_keys = nullptr; c->d_slot = nullptr; c->d_num = nullptr; c->d_mean = nullptr; c->d_cov = nullptr; c->nvox = 0; c->t_alloc = 0; c->v_alloc = 0; }
-static void free_aside(vgicp_ctx* c) { vgicp_ctx::VoxSet& a = c->aside; hipFree(a.keys); hipFree(a.slot); hipFree(a.num); hipFree(a.mean); hipFree(a.cov); hipFree(a.wsq); a = vgicp_ctx::VoxSet(); }
-static void free_source(vgicp_ctx* c) { hipFree(c->d_sxyz); hipFree(c->d_scov); c->d_sxyz = nullptr; c->d_scov = nullptr; c->n = 0; }
-
+// the sums of a linearisation (21 H upper | 6 b | error | count) as the symmetric H and b
+__host__ __device__ static void unpack_Hb(const double* sums, double* H, double* b) {
+    int idx = 0;
+    for (int p = 0; p < 6; ++p) { for (int q = p; q < 6; ++q) { H[6 * p + q] = sums[idx]; H[6 * q + p] = sums[idx]; ++idx; } b[p] = sums[21 + p]; }
+}
 static Iso to_iso(const double* T) { Iso r; for (int q = 0; q < 12; ++q) r.m[q] = T[q]; return r; }
-static VoxTab tab(const vgicp_ctx* c) { return VoxTab{c->d_keys, c->d_slot, c->cap - 1, c->d_num, c->d_mean, c->d_cov, c->d_wsq}; }
+static VoxTab tab(const vgicp_ctx* c) { const VoxSet& v = c->live; return VoxTab{v.keys.p, v.slot.p, v.tcap - 1, v.num.p, v.mean.p, v.cov.p, v.wsq.p}; }
+// the device builder fills the set aside; it becomes the target when that succeeded, any other status leaves the target as it was
+static int build_and_install(vgicp_ctx* c, int n, const float* d_xyz, const double* d_cov9, double resolution) {
+    const int st = build_target_dev(c->aside, c->d_bws, c->bprof, c->h_build, c->stream, n, d_xyz, d_cov9, resolution);
+    if (st == VIL_OK) { std::swap(c->live, c->aside); c->linearized = false; }
+    return st;
+}
+// room for passes over `slots` slots: the first ncache caches, each sized from its own need, and the partial sums of the 256-slot
+// workgroups (k_vgicp_lin; k_vgicp_err after it or after an alignment)
+static int reserve_pass(vgicp_ctx* c, size_t slots, int ncache) {
+    for (int k = 0; k < ncache; ++k) { VILCHK(c->cache[k].vox.reserve(slots, slots)); VILCHK(c->cache[k].M.reserve(9 * slots, 9 * slots)); }
+    const size_t nblk = (slots + VG_THREADS - 1) / VG_THREADS;
+    VILCHK(c->d_part.reserve(29 * nblk, 29 * nblk));
+    return VIL_OK;
+}
 
 // device covariances of a device-resident cloud (d_xyz) into d_cov (n x 9)
 static int covariances_dev(vgicp_ctx* c, int n, const float* d_xyz, int k, double* d_cov) {
@@ -450,10 +339,10 @@ static int covariances_dev(vgicp_ctx* c, int n, const float* d_xyz, int k, doubl
     if (n < grid_min) {
         hipLaunchKernelGGL(k_knn_cov, dim3(nblk), dim3(VG_THREADS), 0, c->stream, n, d_xyz, k, d_cov);
     } else {
-        if ((size_t)n * KNN_MAX * 4 > c->nn_cap) { hipFree(c->d_nn); c->d_nn = nullptr; c->nn_cap = 0; VILCHK(hipMalloc(&c->d_nn, (size_t)n * KNN_MAX * 6)); c->nn_cap = (size_t)n * KNN_MAX * 6; }
+        VILCHK(c->d_nn.reserve((size_t)n * KNN_MAX, (size_t)n * KNN_MAX * 3 / 2));
         VILCHK(vknn::grid_build_adaptive(c->gb, n, d_xyz, 3, c->grid_h, 8.0, c->stream));
-        hipLaunchKernelGGL(k_knn_wave, dim3((n + VG_QPB - 1) / VG_QPB), dim3(64 * VG_QPB), 0, c->stream, n, d_xyz, c->gb.G, c->gb.order, c->gb.cxyz, k, c->d_nn);
-        hipLaunchKernelGGL(k_knn_fit, dim3(nblk), dim3(VG_THREADS), 0, c->stream, n, d_xyz, c->d_nn, k, d_cov);
+        hipLaunchKernelGGL(k_knn_wave, dim3((n + VG_QPB - 1) / VG_QPB), dim3(64 * VG_QPB), 0, c->stream, n, d_xyz, c->gb.G, c->gb.order, c->gb.cxyz, k, c->d_nn.p);
+        hipLaunchKernelGGL(k_knn_fit, dim3(nblk), dim3(VG_THREADS), 0, c->stream, n, d_xyz, c->d_nn.p, k, d_cov);
     }
     VILCHK(hipStreamSynchronize(c->stream));
     VILCHK(hipGetLastError());
@@ -463,79 +352,17 @@ static int covariances_dev(vgicp_ctx* c, int n, const float* d_xyz, int k, doubl
 // the fixed-order sum of the workgroup partials, result in c->h_out: polled from pinned memory (profiling / VIL_NO_POLL: copy + synchronise)
 template <int NV>
 static hipError_t sum_and_fetch(vgicp_ctx* c, int nblk) {
-    if (!c->h_lin && !c->lin_tag && !getenv("VIL_NO_POLL")) {
-        if (hipHostMalloc((void**)&c->h_lin, 8 * 32 + 64, hipHostMallocMapped) == hipSuccess) {
-            memset(c->h_lin, 0, 8 * 32 + 64);
-            if (hipHostGetDevicePointer(&c->d_lin, c->h_lin, 0) != hipSuccess) { hipHostFree(c->h_lin); c->h_lin = nullptr; c->d_lin = nullptr; }
-        } else c->h_lin = nullptr;
-        c->lin_tag = 1;
-    }
-    if (c->h_lin && !c->prof.on) {
+    if (!c->lin_tag && !getenv("VIL_NO_POLL")) { c->lin.open(8 * 32 + 64); c->lin_tag = 1; }      // one attempt; without the record: copy + synchronise
+    if (c->lin.h && !c->prof.on) {
         const int tag = ++c->lin_tag;
-        volatile int* seq = (volatile int*)(c->h_lin + 8 * 32);
-        hipLaunchKernelGGL((k_vgicp_sum<NV>), dim3(1), dim3(VG_THREADS), 0, c->stream, nblk, c->d_part, c->d_out, (double*)c->d_lin, (int*)((char*)c->d_lin + 8 * 32), tag);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (long spin = 1;; ++spin) {
-            if (*seq == tag) { seen = true; break; }
-            if ((spin & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-        }
-        if (seen) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_out, c->h_lin, 8 * NV); return hipSuccess; }
+        hipLaunchKernelGGL((k_vgicp_sum<NV>), dim3(1), dim3(VG_THREADS), 0, c->stream, nblk, c->d_part.p, c->d_out, (double*)c->lin.d, (int*)((char*)c->lin.d + 8 * 32), tag);
+        if (vilhost::await_word((volatile int*)(c->lin.h + 8 * 32), tag, 200)) { memcpy(c->h_out, c->lin.h, 8 * NV); return hipSuccess; }
         const hipError_t e = hipStreamSynchronize(c->stream);       // surfaces a fault; a merely slow device gets the copy below
         if (e != hipSuccess) return e;
-    } else hipLaunchKernelGGL((k_vgicp_sum<NV>), dim3(1), dim3(VG_THREADS), 0, c->stream, nblk, c->d_part, c->d_out, (double*)nullptr, (int*)nullptr, 0);
+    } else hipLaunchKernelGGL((k_vgicp_sum<NV>), dim3(1), dim3(VG_THREADS), 0, c->stream, nblk, c->d_part.p, c->d_out, (double*)nullptr, (int*)nullptr, 0);
     hipError_t e = hipMemcpyAsync(c->h_out, c->d_out, 8 * NV, hipMemcpyDeviceToHost, c->stream);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(c->stream);
-}
-
-// The target map of n device-resident points and covariances, built aside and swapped in: on VIL_ERR_NON_FINITE (or a HIP error) the
-// previous target is untouched.  Seven launches, then ONE host wait for the voxel count and the non-finite flag.
-static int build_target_dev(vgicp_ctx* c, int n, const float* d_xyz, const double* d_cov9, double resolution) {
-    if (n > (1 << 28)) return VIL_ERR_CAPACITY;          // (2 n table slots and 12 n lanes stay below 2^31 with room to spare)
-    int tcap = 64; while (tcap < 2 * n) tcap <<= 1;     // sized from n: the number of voxels is not known on the host
-    vgicp_ctx::VoxSet& a = c->aside;
-    if (a.t_alloc < tcap || a.v_alloc < n) {
-        free_aside(c);
-        const size_t v = (size_t)n + (size_t)n / 2;      // head room: the next scans are about this size
-        VILCHK(hipMalloc(&a.keys, 8 * (size_t)tcap)); VILCHK(hipMalloc(&a.slot, 4 * (size_t)tcap)); VILCHK(hipMalloc(&a.num, 4 * v));
-        VILCHK(hipMalloc(&a.mean, 8 * 3 * v)); VILCHK(hipMalloc(&a.cov, 8 * 9 * v)); VILCHK(hipMalloc(&a.wsq, 8 * v));
-        a.t_alloc = tcap; a.v_alloc = (int)v;
-    }
-    const int nb = (n + VG_THREADS - 1) / VG_THREADS;
-    vilhost::Arena ar;
-    const size_t o_cnt = ar.take(4 * (size_t)tcap), o_cur = ar.take(4 * (size_t)tcap), o_start = ar.take(4 * (size_t)tcap), o_first = ar.take(4 * (size_t)tcap);
-    const size_t o_pslot = ar.take(4 * (size_t)n), o_member = ar.take(4 * (size_t)n), o_sorted = ar.take(4 * (size_t)n), o_vstart = ar.take(4 * (size_t)n);
-    const size_t o_bsum = ar.take(4 * (size_t)nb), o_boff = ar.take(4 * (size_t)nb), o_ctr = ar.take(16);
-    if (ar.bytes > c->bws_bytes) {
-        hipFree(c->d_bws); c->d_bws = nullptr; c->bws_bytes = 0;
-        const size_t want = ar.bytes + ar.bytes / 2;
-        VILCHK(hipMalloc(&c->d_bws, want));
-        c->bws_bytes = want;
-    }
-    char* w = c->d_bws;
-    VoxBuild B{a.keys, a.slot, tcap - 1, (int*)(w + o_cnt), (int*)(w + o_cur), (int*)(w + o_start), (unsigned*)(w + o_first),
-               (int*)(w + o_pslot), (int*)(w + o_member), (int*)(w + o_sorted), (int*)(w + o_vstart), (int*)(w + o_bsum), (int*)(w + o_boff), (int*)(w + o_ctr),
-               a.num, a.mean, a.cov, a.wsq};
-    const dim3 T(VG_THREADS), Gt((tcap + VG_THREADS - 1) / VG_THREADS), Gn(nb), Gs((unsigned)((12 * (size_t)n + VG_THREADS - 1) / VG_THREADS));
-    hipStream_t s = c->stream;
-    VILCHK(c->bprof.mark(0, s)); hipLaunchKernelGGL(k_vox_clear, Gt, T, 0, s, tcap, B);
-    VILCHK(c->bprof.mark(1, s)); hipLaunchKernelGGL(k_vox_insert, Gn, T, 0, s, n, d_xyz, resolution, B);
-    VILCHK(c->bprof.mark(2, s)); hipLaunchKernelGGL(k_vox_offsets, Gt, T, 0, s, tcap, B);
-    VILCHK(c->bprof.mark(3, s)); hipLaunchKernelGGL(k_vox_fill, Gn, T, 0, s, n, B);
-    VILCHK(c->bprof.mark(4, s)); hipLaunchKernelGGL(k_vox_scan, dim3(1), T, 0, s, nb, B);
-    VILCHK(c->bprof.mark(5, s)); hipLaunchKernelGGL(k_vox_rank, Gn, T, 0, s, n, B);
-    VILCHK(c->bprof.mark(6, s)); hipLaunchKernelGGL(k_vox_sum, Gs, T, 0, s, d_xyz, d_cov9, B);
-    VILCHK(c->bprof.mark(7, s));
-    VILCHK(hipMemcpyAsync(c->h_build, B.ctr + 1, 8, hipMemcpyDeviceToHost, s));
-    VILCHK(hipStreamSynchronize(s));
-    VILCHK(hipGetLastError());
-    for (int k = 0; k < VGICP_BUILD_KERNELS; ++k) c->bprof.span(k, k, k + 1);
-    if (c->h_build[1]) return VIL_ERR_NON_FINITE;
-    std::swap(c->d_keys, a.keys); std::swap(c->d_slot, a.slot); std::swap(c->d_num, a.num); std::swap(c->d_mean, a.mean); std::swap(c->d_cov, a.cov); std::swap(c->d_wsq, a.wsq);
-    std::swap(c->t_alloc, a.t_alloc); std::swap(c->v_alloc, a.v_alloc);
-    c->res = resolution; c->nvox = c->h_build[0]; c->cap = tcap; c->linearized = false;
-    return VIL_OK;
 }
 
 extern "C" {
@@ -543,12 +370,11 @@ extern "C" {
 int vgicp_covariances(vgicp_ctx* c, int32_t n, const float* xyz, int32_t k, double* out) {
     if (!c || n <= 0 || !xyz || !out) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    float* dx = nullptr; double* dc = nullptr;
-    VILCHK(hipMalloc(&dx, 12 * (size_t)n));
-    if (hipMalloc(&dc, 72 * (size_t)n) != hipSuccess) { hipFree(dx); return VIL_ERR_DEVICE; }
-    int st = hipMemcpy(dx, xyz, 12 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess ? covariances_dev(c, n, dx, k, dc) : VIL_ERR_DEVICE;
-    if (st == VIL_OK && hipMemcpy(out, dc, 72 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) st = VIL_ERR_DEVICE;
-    hipFree(dx); hipFree(dc);
+    vilhost::Grown<float> dx; vilhost::Grown<double> dc;      // of this call: freed on every way out
+    VILCHK(dx.reserve(3 * (size_t)n, 3 * (size_t)n)); VILCHK(dc.reserve(9 * (size_t)n, 9 * (size_t)n));
+    VILCHK(hipMemcpy(dx.p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice));
+    const int st = covariances_dev(c, n, dx.p, k, dc.p);
+    if (st == VIL_OK) VILCHK(hipMemcpy(out, dc.p, 72 * (size_t)n, hipMemcpyDeviceToHost));
     return st;
 }
 
@@ -565,13 +391,8 @@ int vgicp_create(int32_t device, vgicp_ctx** out) {
 }
 void vgicp_destroy(vgicp_ctx* c) {
     if (!c) return;
-    hipSetDevice(c->device);
-    free_target(c); free_source(c); free_aside(c);
-    hipFree(c->d_bws); hipFree(c->d_txyz); hipFree(c->d_tcov); c->bprof.destroy();
-    hipFree(c->d_cvox); hipFree(c->d_cM); hipFree(c->d_cvox2); hipFree(c->d_cM2); hipFree(c->d_part);
-    hipFree(c->gb.ws); hipFree(c->d_nn);
-    if (c->d_coop) hipFree(c->d_coop); if (c->h_aout) hipHostFree(c->h_aout); if (c->h_lin) hipHostFree(c->h_lin);
     c->close(c->prof);
+    c->bprof.destroy();                                    // (the device close() selected is still current)
     delete c;
 }
 void vgicp_default_options(vgicp_options* o) {
@@ -584,16 +405,12 @@ int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* co
     if (!c || n <= 0 || !xyz || !(resolution > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     if (c->builder == VGICP_BUILD_DEVICE) {               // points (and given covariances) up, everything else on the device
-        if ((size_t)n > c->tpts_cap) {
-            hipFree(c->d_txyz); hipFree(c->d_tcov); c->d_txyz = nullptr; c->d_tcov = nullptr; c->tpts_cap = 0;
-            const size_t cap = (size_t)n + (size_t)n / 2;
-            VILCHK(hipMalloc(&c->d_txyz, 12 * cap)); VILCHK(hipMalloc(&c->d_tcov, 72 * cap));
-            c->tpts_cap = cap;
-        }
-        VILCHK(hipMemcpyAsync(c->d_txyz, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        if (cov9_in) VILCHK(hipMemcpyAsync(c->d_tcov, cov9_in, 72 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        else { const int st = covariances_dev(c, n, c->d_txyz, KNN_MAX, c->d_tcov); if (st != VIL_OK) return st; }
-        return build_target_dev(c, n, c->d_txyz, c->d_tcov, resolution);
+        const size_t cap = (size_t)n + (size_t)n / 2;
+        VILCHK(c->d_txyz.reserve(3 * (size_t)n, 3 * cap)); VILCHK(c->d_tcov.reserve(9 * (size_t)n, 9 * cap));
+        VILCHK(hipMemcpyAsync(c->d_txyz.p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        if (cov9_in) VILCHK(hipMemcpyAsync(c->d_tcov.p, cov9_in, 72 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        else { const int st = covariances_dev(c, n, c->d_txyz.p, KNN_MAX, c->d_tcov.p); if (st != VIL_OK) return st; }
+        return build_and_install(c, n, c->d_txyz.p, c->d_tcov.p, resolution);
     }
     std::vector<double> own;
     const double* cov9 = cov9_in;
@@ -619,14 +436,17 @@ int vgicp_set_target(vgicp_ctx* c, int32_t n, const float* xyz, const double* co
     int cap = 64; while (cap < 2 * nv) cap <<= 1;
     std::vector<long long> tkeys((size_t)cap, -1); std::vector<int> tslot((size_t)cap, -1);
     for (int v = 0; v < nv; ++v) { unsigned h = hash_key(keys[v]) & (cap - 1); while (tkeys[h] >= 0) h = (h + 1) & (cap - 1); tkeys[h] = keys[v]; tslot[h] = v; }
-    free_target(c);
-    VILCHK(hipMalloc(&c->d_keys, 8 * (size_t)cap)); VILCHK(hipMalloc(&c->d_slot, 4 * (size_t)cap)); VILCHK(hipMalloc(&c->d_num, 4 * (size_t)nv));
-    VILCHK(hipMalloc(&c->d_mean, 8 * 3 * (size_t)nv)); VILCHK(hipMalloc(&c->d_cov, 8 * 9 * (size_t)nv));
-    VILCHK(hipMemcpy(c->d_keys, tkeys.data(), 8 * (size_t)cap, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(c->d_slot, tslot.data(), 4 * (size_t)cap, hipMemcpyHostToDevice));
-    { std::vector<double> wsq((size_t)nv); for (int v = 0; v < nv; ++v) wsq[v] = std::sqrt((double)num[v]); VILCHK(hipMalloc(&c->d_wsq, 8 * (size_t)nv)); VILCHK(hipMemcpy(c->d_wsq, wsq.data(), 8 * (size_t)nv, hipMemcpyHostToDevice)); }
-    VILCHK(hipMemcpy(c->d_num, num.data(), 4 * (size_t)nv, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(c->d_mean, mean.data(), 8 * 3 * (size_t)nv, hipMemcpyHostToDevice));
-    VILCHK(hipMemcpy(c->d_cov, cov.data(), 8 * 9 * (size_t)nv, hipMemcpyHostToDevice));
-    c->res = resolution; c->nvox = nv; c->cap = cap; c->linearized = false; c->t_alloc = cap; c->v_alloc = nv;
+    // into the set aside, as the device builder: a failed allocation or copy leaves the previous target in place
+    VoxSet& a = c->aside;
+    const size_t sc = (size_t)cap, sv = (size_t)nv;
+    VILCHK(a.keys.reserve(sc, sc)); VILCHK(a.slot.reserve(sc, sc)); VILCHK(a.num.reserve(sv, sv));
+    VILCHK(a.mean.reserve(3 * sv, 3 * sv)); VILCHK(a.cov.reserve(9 * sv, 9 * sv)); VILCHK(a.wsq.reserve(sv, sv));
+    VILCHK(hipMemcpy(a.keys.p, tkeys.data(), 8 * sc, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(a.slot.p, tslot.data(), 4 * sc, hipMemcpyHostToDevice));
+    { std::vector<double> wsq(sv); for (int v = 0; v < nv; ++v) wsq[v] = std::sqrt((double)num[v]); VILCHK(hipMemcpy(a.wsq.p, wsq.data(), 8 * sv, hipMemcpyHostToDevice)); }
+    VILCHK(hipMemcpy(a.num.p, num.data(), 4 * sv, hipMemcpyHostToDevice)); VILCHK(hipMemcpy(a.mean.p, mean.data(), 8 * 3 * sv, hipMemcpyHostToDevice));
+    VILCHK(hipMemcpy(a.cov.p, cov.data(), 8 * 9 * sv, hipMemcpyHostToDevice));
+    a.tcap = cap; a.nvox = nv; a.res = resolution;
+    std::swap(c->live, c->aside); c->linearized = false;
     return VIL_OK;
 }
 
@@ -639,26 +459,27 @@ int vgicp_set_voxel_builder(vgicp_ctx* c, int32_t builder) {
 int vgicp_promote_source(vgicp_ctx* c, double resolution) {
     if (!c || !c->n || !(resolution > 0.0)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    return build_target_dev(c, c->n, c->d_sxyz, c->d_scov, resolution);
+    return build_and_install(c, c->n, c->d_sxyz.p, c->d_scov.p, resolution);
 }
 
 // voxel order from the table: the slot of a key holds the voxel's number, whichever builder made the table
 int vgicp_read_voxels(vgicp_ctx* c, vgicp_voxels* out) {
     if (!c || !out) return VIL_ERR_INVALID_ARGUMENT;
-    const int nv = c->nvox;
+    const VoxSet& v = c->live;
+    const int nv = v.nvox;
     out->count = nv;
     if (out->capacity < nv) return VIL_ERR_INVALID_ARGUMENT;
     if (!nv) return VIL_OK;
     VILCHK(hipSetDevice(c->device));
     if (out->keys) {
-        std::vector<long long> tkeys((size_t)c->cap); std::vector<int> tslot((size_t)c->cap);
-        VILCHK(hipMemcpy(tkeys.data(), c->d_keys, 8 * (size_t)c->cap, hipMemcpyDeviceToHost)); VILCHK(hipMemcpy(tslot.data(), c->d_slot, 4 * (size_t)c->cap, hipMemcpyDeviceToHost));
-        for (int h = 0; h < c->cap; ++h) if (tkeys[h] >= 0 && tslot[h] >= 0 && tslot[h] < nv) out->keys[tslot[h]] = (int64_t)tkeys[h];
+        std::vector<long long> tkeys((size_t)v.tcap); std::vector<int> tslot((size_t)v.tcap);
+        VILCHK(hipMemcpy(tkeys.data(), v.keys.p, 8 * (size_t)v.tcap, hipMemcpyDeviceToHost)); VILCHK(hipMemcpy(tslot.data(), v.slot.p, 4 * (size_t)v.tcap, hipMemcpyDeviceToHost));
+        for (int h = 0; h < v.tcap; ++h) if (tkeys[h] >= 0 && tslot[h] >= 0 && tslot[h] < nv) out->keys[tslot[h]] = (int64_t)tkeys[h];
     }
-    if (out->num) VILCHK(hipMemcpy(out->num, c->d_num, 4 * (size_t)nv, hipMemcpyDeviceToHost));
-    if (out->mean3) VILCHK(hipMemcpy(out->mean3, c->d_mean, 8 * 3 * (size_t)nv, hipMemcpyDeviceToHost));
-    if (out->cov9) VILCHK(hipMemcpy(out->cov9, c->d_cov, 8 * 9 * (size_t)nv, hipMemcpyDeviceToHost));
-    if (out->wsq) VILCHK(hipMemcpy(out->wsq, c->d_wsq, 8 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->num) VILCHK(hipMemcpy(out->num, v.num.p, 4 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->mean3) VILCHK(hipMemcpy(out->mean3, v.mean.p, 8 * 3 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->cov9) VILCHK(hipMemcpy(out->cov9, v.cov.p, 8 * 9 * (size_t)nv, hipMemcpyDeviceToHost));
+    if (out->wsq) VILCHK(hipMemcpy(out->wsq, v.wsq.p, 8 * (size_t)nv, hipMemcpyDeviceToHost));
     return VIL_OK;
 }
 
@@ -676,24 +497,23 @@ int vgicp_build_profile_read(vgicp_ctx* c, int64_t* launches, double* total_ms) 
 int vgicp_set_source(vgicp_ctx* c, int32_t n, const float* xyz, const double* cov9) {
     if (!c || n <= 0 || !xyz) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    free_source(c);
-    VILCHK(hipMalloc(&c->d_sxyz, 4 * 3 * (size_t)n)); VILCHK(hipMalloc(&c->d_scov, 8 * 9 * (size_t)n));
-    VILCHK(hipMemcpy(c->d_sxyz, xyz, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
-    if (cov9) VILCHK(hipMemcpy(c->d_scov, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
-    else { const int st = covariances_dev(c, n, c->d_sxyz, KNN_MAX, c->d_scov); if (st != VIL_OK) return st; }      // source covariances never leave the device
+    c->n = 0;                                              // no source until this one is complete
+    VILCHK(c->d_sxyz.reserve(3 * (size_t)n, 3 * (size_t)n)); VILCHK(c->d_scov.reserve(9 * (size_t)n, 9 * (size_t)n));
+    VILCHK(hipMemcpy(c->d_sxyz.p, xyz, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
+    if (cov9) VILCHK(hipMemcpy(c->d_scov.p, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
+    else { const int st = covariances_dev(c, n, c->d_sxyz.p, KNN_MAX, c->d_scov.p); if (st != VIL_OK) return st; }      // source covariances never leave the device
     c->n = n; c->linearized = false;
     return VIL_OK;
 }
 
 int vgicp_linearize(vgicp_ctx* c, const double* T, int32_t mode, double* err, double* H, double* b, int32_t* n_corr) {
-    if (!c || !T || !err || !c->nvox || !c->n || (mode != VGICP_DIRECT1 && mode != VGICP_DIRECT7 && mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c || !T || !err || !c->live.nvox || !c->n || (mode != VGICP_DIRECT1 && mode != VGICP_DIRECT7 && mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     const int slots = c->n * mode, nblk = (slots + VG_THREADS - 1) / VG_THREADS;
-    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VILCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VILCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
-    if (nblk > c->part_cap) { hipFree(c->d_part); c->d_part = nullptr; c->part_cap = 0; VILCHK(hipMalloc(&c->d_part, 8 * 29 * (size_t)nblk)); c->part_cap = nblk; }
+    if (reserve_pass(c, (size_t)slots, 1) != VIL_OK) return VIL_ERR_DEVICE;
     const int want = (H && b) ? 1 : 0;
     VILCHK(c->prof.mark(0, c->stream));
-    hipLaunchKernelGGL(k_vgicp_lin, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->n, (int)mode, c->d_sxyz, c->d_scov, to_iso(T), c->res, tab(c), c->d_cvox, c->d_cM, c->d_part, want);
+    hipLaunchKernelGGL(k_vgicp_lin, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->n, (int)mode, c->d_sxyz.p, c->d_scov.p, to_iso(T), c->live.res, tab(c), c->cache[0].vox.p, c->cache[0].M.p, c->d_part.p, want);
     VILCHK(c->prof.mark(1, c->stream));
     VILCHK(sum_and_fetch<29>(c, nblk));
     VILCHK(hipGetLastError());
@@ -701,10 +521,7 @@ int vgicp_linearize(vgicp_ctx* c, const double* T, int32_t mode, double* err, do
     c->noff = mode; c->slots = slots; c->linearized = true;
     *err = c->h_out[27];
     if (n_corr) *n_corr = (int32_t)c->h_out[28];
-    if (want) {
-        int idx = 0;
-        for (int p = 0; p < 6; ++p) { for (int q = p; q < 6; ++q) { H[6 * p + q] = c->h_out[idx]; H[6 * q + p] = c->h_out[idx]; ++idx; } b[p] = c->h_out[21 + p]; }
-    }
+    if (want) unpack_Hb(c->h_out, H, b);
     return std::isfinite(*err) ? VIL_OK : VIL_ERR_NON_FINITE;
 }
 
@@ -723,7 +540,7 @@ int vgicp_compute_error(vgicp_ctx* c, const double* T, double* err) {
     if (!c || !T || !err || !c->linearized) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     const int nblk = (c->slots + VG_THREADS - 1) / VG_THREADS;
-    hipLaunchKernelGGL(k_vgicp_err, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->slots, c->noff, c->d_sxyz, to_iso(T), tab(c), c->d_cvox, c->d_cM, c->d_part);
+    hipLaunchKernelGGL(k_vgicp_err, dim3(nblk), dim3(VG_THREADS), 0, c->stream, c->slots, c->noff, c->d_sxyz.p, to_iso(T), tab(c), c->cache[0].vox.p, c->cache[0].M.p, c->d_part.p);
     VILCHK(sum_and_fetch<1>(c, nblk));
     *err = c->h_out[0];
     return std::isfinite(*err) ? VIL_OK : VIL_ERR_NON_FINITE;
@@ -753,16 +570,8 @@ __host__ __device__ static void so3_exp_R(const double* w, double* R) {      // 
     const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz, twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
     R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy; R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx; R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
-__host__ __device__ static void compose(const double* d, const double* x0, double* xi) {
-    double R[9]; so3_exp_R(d, R);
-    for (int r = 0; r < 3; ++r) {
-        for (int q = 0; q < 4; ++q) xi[4 * r + q] = R[3 * r] * x0[q] + R[3 * r + 1] * x0[4 + q] + R[3 * r + 2] * x0[8 + q];
-        xi[4 * r + 3] += d[3 + r];
-    }
-    xi[12] = 0; xi[13] = 0; xi[14] = 0; xi[15] = 1;
-}
-// the same two with the increment's rotation matrix shared (the device loop calls both on the same d: one sin / cos less per pass)
-__device__ static void compose_R(const double* d, const double* x0, double* xi, double* R) {
+// xi = exp(d) x0; R: the increment's rotation matrix, which the device loop hands on to converged_R (one sin / cos less per pass)
+__host__ __device__ static void compose_R(const double* d, const double* x0, double* xi, double* R) {
     so3_exp_R(d, R);
     for (int r = 0; r < 3; ++r) {
         for (int q = 0; q < 4; ++q) xi[4 * r + q] = R[3 * r] * x0[q] + R[3 * r + 1] * x0[4 + q] + R[3 * r + 2] * x0[8 + q];
@@ -770,6 +579,7 @@ __device__ static void compose_R(const double* d, const double* x0, double* xi, 
     }
     xi[12] = 0; xi[13] = 0; xi[14] = 0; xi[15] = 1;
 }
+static void compose(const double* d, const double* x0, double* xi) { double R[9]; compose_R(d, x0, xi, R); }
 // is_converged without its twelve divides (one lane, every workgroup waiting): for eps > 0, fl(a / eps) < 1 exactly when a < eps
 // (a < eps: the quotient is below 1 and rounds to at most the largest double below 1; a >= eps: it is at least 1), and the
 // maximum is below 1 exactly when every term is -- the same decision, bit for bit
@@ -847,8 +657,7 @@ __device__ static bool solve6_dev(const double* A, const double* rhs, double* x)
 // consumes the sums of the pass just exchanged, returns the next pass (0 = finished); mirrors the host loop statement by statement
 __device__ static int vg_lm_advance(VgLm& L, const double* tot, const vgicp_options& o) {
     if (L.phase == 1) {
-        int idx = 0;
-        for (int p = 0; p < 6; ++p) { for (int q = p; q < 6; ++q) { L.H[6 * p + q] = tot[idx]; L.H[6 * q + p] = tot[idx]; ++idx; } L.b[p] = tot[21 + p]; }
+        unpack_Hb(tot, L.H, L.b);
         L.y0 = tot[27]; L.n_corr = (int)tot[28];
         double nb[6];
         for (int k = 0; k < 6; ++k) { nb[k] = -L.b[k]; L.d[k] = 0.0; }
@@ -888,8 +697,7 @@ __device__ static int vg_lm_advance(VgLm& L, const double* tot, const vgicp_opti
             // x0 = xi: the pass that judged the trial has linearised there already (tot[0 .. 29), correspondences in the other cache)
             if (!isfinite(tot[27])) { L.lm_failed = -1; return 0; }
             L.flip = 1;
-            int idx = 0;
-            for (int p = 0; p < 6; ++p) { for (int q = p; q < 6; ++q) { L.H[6 * p + q] = tot[idx]; L.H[6 * q + p] = tot[idx]; ++idx; } L.b[p] = tot[21 + p]; }
+            unpack_Hb(tot, L.H, L.b);
             L.y0 = tot[27]; L.n_corr = (int)tot[28];
             L.nu = 2.0; L.inner = 0;
         }
@@ -1040,14 +848,19 @@ int vgicp_set_knn_grid(vgicp_ctx* c, int32_t min_points, double cell) {
 
 int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, double* T_out, vgicp_summary* out) {
     if (!c || !guess || !o || !T_out || !out) return VIL_ERR_INVALID_ARGUMENT;
-    if (!c->nvox || !c->n || (o->neighbor_mode != VGICP_DIRECT1 && o->neighbor_mode != VGICP_DIRECT7 && o->neighbor_mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c->live.nvox || !c->n || (o->neighbor_mode != VGICP_DIRECT1 && o->neighbor_mode != VGICP_DIRECT7 && o->neighbor_mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
     if (VIL_TUNE_ENV("VGICP_HOST_LOOP")) return vgicp_align_host(c, guess, o, T_out, out);       // the step logic on the host between launches (cross-check)
     VILCHK(hipSetDevice(c->device));
     const int mode = o->neighbor_mode, slots = c->n * mode, nblk = (slots + VGA_THREADS - 1) / VGA_THREADS;
-    if (slots > c->slots_cap) { hipFree(c->d_cvox); hipFree(c->d_cM); c->d_cvox = nullptr; c->d_cM = nullptr; c->slots_cap = 0; VILCHK(hipMalloc(&c->d_cvox, 4 * (size_t)slots)); VILCHK(hipMalloc(&c->d_cM, 8 * 9 * (size_t)slots)); c->slots_cap = slots; }
-    if (slots > c->slots_cap2) { hipFree(c->d_cvox2); hipFree(c->d_cM2); c->d_cvox2 = nullptr; c->d_cM2 = nullptr; c->slots_cap2 = 0; VILCHK(hipMalloc(&c->d_cvox2, 4 * (size_t)c->slots_cap)); VILCHK(hipMalloc(&c->d_cM2, 8 * 9 * (size_t)c->slots_cap)); c->slots_cap2 = c->slots_cap; }
-    if (!c->d_coop) { VILCHK(hipMalloc(&c->d_coop, sizeof(VgCoop))); VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); VILCHK(hipHostMalloc(&c->h_aout, sizeof(VgAlignOut), hipHostMallocMapped)); VILCHK(hipHostGetDevicePointer(&c->d_aout, c->h_aout, 0)); c->coop_epoch = 0; }
-    VgAlignOut* ho = (VgAlignOut*)c->h_aout;
+    if (reserve_pass(c, (size_t)slots, 2) != VIL_OK) return VIL_ERR_DEVICE;
+    if (!c->d_coop.p) {                                    // the workgroups' meeting point (zeroed) and the result record: both or neither
+        hipError_t e = c->d_coop.reserve(sizeof(VgCoop), sizeof(VgCoop));
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_coop.p, 0, sizeof(VgCoop), c->stream);
+        if (e == hipSuccess) e = c->aout.open(sizeof(VgAlignOut));
+        if (e != hipSuccess) { c->d_coop.release(); c->aout.release(); VILCHK(e); }
+        c->coop_epoch = 0;
+    }
+    VgAlignOut* ho = (VgAlignOut*)c->aout.h;
     VgGuess gs; std::memcpy(gs.m, guess, sizeof gs.m);
     if (c->coop_cap < 0) c->coop_cap = vilcoop::capacity((const void*)k_vgicp_align, VGA_THREADS, 0, c->device);
     if (c->coop_cap < 1) return vgicp_align_host(c, guess, o, T_out, out);      // the kernel cannot be resident on this device: one launch per pass instead
@@ -1056,24 +869,16 @@ int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, doubl
     if (const char* ev = VIL_TUNE_ENV("VGICP_G")) G = std::max(1, std::min(VG_MAXG, atoi(ev)));
     const int epoch_of_call = c->coop_epoch;
     ho->seq = -1;
-    hipLaunchKernelGGL(k_vgicp_align, dim3(G), dim3(VGA_THREADS), 0, c->stream, c->n, mode, c->d_sxyz, c->d_scov, c->res, tab(c), c->d_cvox, c->d_cM, c->d_cvox2, c->d_cM2, *o, (VgCoop*)c->d_coop, c->coop_epoch, gs, (VgAlignOut*)c->d_aout);
+    hipLaunchKernelGGL(k_vgicp_align, dim3(G), dim3(VGA_THREADS), 0, c->stream, c->n, mode, c->d_sxyz.p, c->d_scov.p, c->live.res, tab(c), c->cache[0].vox.p, c->cache[0].M.p, c->cache[1].vox.p, c->cache[1].M.p,
+                       *o, (VgCoop*)c->d_coop.p, c->coop_epoch, gs, (VgAlignOut*)c->aout.d);
     c->coop_epoch += 4 * (o->max_iterations * (o->lm_max_iterations + 1) + 4);      // epochs only grow: nothing to reset between calls
-    if (c->coop_epoch > (1 << 30)) { VILCHK(hipMemsetAsync(c->d_coop, 0, sizeof(VgCoop), c->stream)); c->coop_epoch = 0; }
-    {   // the kernel's last act is the record's sequence number in pinned memory: polling it returns a few microseconds before the
-        // stream's completion signal would (the launch queue stays in order either way); a kernel that never gets there is left to
-        // hipStreamSynchronize, which reports the fault
-        volatile int* seq = &ho->seq;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (long spin = 0;; ++spin) {
-            if (*seq == epoch_of_call + 1) { seen = true; break; }
-            if ((spin & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-        }
-        if (!seen) VILCHK(hipStreamSynchronize(c->stream));
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    if (c->coop_epoch > (1 << 30)) { VILCHK(hipMemsetAsync(c->d_coop.p, 0, sizeof(VgCoop), c->stream)); c->coop_epoch = 0; }
+    // the kernel's last act is the record's sequence number in pinned memory: polling it returns a few microseconds before the
+    // stream's completion signal would (the launch queue stays in order either way); a kernel that never gets there is left to
+    // hipStreamSynchronize, which reports the fault
+    if (!vilhost::await_word(&ho->seq, epoch_of_call + 1, 200)) VILCHK(hipStreamSynchronize(c->stream));
     VILCHK(hipGetLastError());
-    if (ho->pad) { std::swap(c->d_cvox, c->d_cvox2); std::swap(c->d_cM, c->d_cM2); std::swap(c->slots_cap, c->slots_cap2); }      // vgicp_error() after an alignment sees its last linearisation
+    if (ho->pad) std::swap(c->cache[0], c->cache[1]);      // vgicp_error() after an alignment sees its last linearisation
     c->noff = mode; c->slots = slots; c->linearized = true;
     std::memset(out, 0, sizeof *out);
     out->iterations = ho->iterations; out->converged = ho->converged; out->n_correspondences = ho->n_corr; out->lm_failed = ho->lm_failed; out->final_error = ho->err;

@@ -115,6 +115,26 @@ def test_interleaved_calls_and_map_updates(hip, setup):
     for (qa, ta, sa) in ((q2, t2, s2), (q3, t3, s3)):
         assert (sa.n_edge, sa.n_plane, sa.iterations) == (s1.n_edge, s1.n_plane, s1.iterations)        # (counts of the second round)
         assert np.abs(ta - t1).max() < 1e-10 and np.abs(qa - q1).max() < 1e-10
+    # the map replaced on the long-lived handle -- the module's, its first tenth, the module's again -- against a fresh handle each time
+    cm, sm = mapreg.make_map(seed=4, n_surf=12000, n_corner=2000)
+    for cmap, smap in ((cm, sm), (cm[:len(cm) // 10], sm[:len(sm) // 10]), (cm, sm)):
+        g.set_map(cmap, smap)
+        fresh = mapreg.MapReg(lib.load_vilsolve(), "vmap_")
+        try:
+            fresh.set_map(cmap, smap)
+            ef, pf = fresh.associate(sc, ss, q0, t0)
+        finally:
+            fresh.close()
+        eg, pg = g.associate(sc, ss, q0, t0)
+        assert np.array_equal(eg, ef) and np.array_equal(pg, pf), len(cmap)
+    assert np.array_equal(eg, e) and np.array_equal(pg, p)      # the module's map is back
+    g.profile_enable(True); g.profile_read()
+    try:
+        g.associate(sc, ss, q0, t0)
+        prof = g.profile_read()
+    finally:
+        g.profile_enable(False)
+    assert prof["k_map_search"][0] == 1 and prof["k_map_fit"][0] == 1
 
 
 @pytest.fixture(scope="module")

@@ -145,6 +145,44 @@ def test_covariances_grid_search_parity(oracle, monkeypatch):
     o.close()
 
 
+def test_reuse_across_sources_and_neighbour_modes():
+    """One long-lived context against a fresh one at every step, byte for byte, while the source size and the neighbour mode change
+    under it: 300 slots fit one workgroup of k_vgicp_align, 1025 x 27 take 55; 257 and 1025 straddle the 256-thread blocks; the
+    order grows both correspondence caches, shrinks, then regrows them.  Given covariances, then the brute-force k-NN estimate, then
+    the largest source once more through the grid search."""
+    import ctypes as C
+    from test_gpu_voxelmap import T_SMALL, lin_bytes, same
+    tx, tc, sx, sc, _ = vgicp.make_pair(seed=5, rings=4, az=300)
+    assert len(tx) == 1200 and len(sx) >= 1025
+    so = lib.load_vilsolve()
+
+    def observe(g, mode):
+        T, s = g.align(np.eye(4), g.default_options(neighbor_mode=mode))
+        summary = (s.iterations, s.converged, s.n_correspondences, s.lm_failed, np.float64(s.final_error).tobytes(), bytes(s.final_hessian))
+        return T, summary, np.float64(g.compute_error(T_SMALL)).tobytes(), lin_bytes(g, T_SMALL, mode)      # the error reads the cache the alignment ended in
+
+    steps = [(n, mode, given, False) for given in (True, False) for n, mode in ((300, 1), (1025, 27), (257, 7), (1025, 1), (300, 27))]
+    steps.append((1025, 27, False, True))
+    used = vgicp.Vgicp(so)
+    try:
+        used.set_target(tx, tc, 0.5)
+        for n, mode, given, grid in steps:
+            fresh = vgicp.Vgicp(so)
+            try:
+                fresh.set_target(tx, tc, 0.5)
+                for g in (used, fresh):
+                    if grid:
+                        assert g.lib.vgicp_set_knn_grid(g.ctx, 0, C.c_double(1.0)) == 0
+                    g.set_source(sx[:n], sc[:n] if given else None)
+                a, b = observe(used, mode), observe(fresh, mode)
+            finally:
+                fresh.close()
+            assert same(a[0], b[0]) and a[1:] == b[1:], (n, mode, given, grid)
+            assert a[1][2] > 0 and a[3][1] > 0, (n, mode, given, grid)          # (correspondences were found: the comparison is not of empty sums)
+    finally:
+        used.close()
+
+
 def test_reference_known_answer(oracle):
     """fast_gicp's own registration test data: the GPU passes it, and lands on the oracle's transforms."""
     from test_oracle_vgicp import _kat
