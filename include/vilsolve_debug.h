@@ -47,6 +47,7 @@ int vil_debug_set_slim_emul(vil_ctx* ctx, int32_t on);
  * one-launch iteration runs (16-wide panels factored a matrix row per lane, back substitution a column per lane: vil_step.hpp chol_rowwave / back_subst_cols);
  * variant 0: the look-ahead factorisation (4-wide panels) and the back substitution through inverted diagonal tiles that the other launch structures run. */
 int vil_debug_dense_solve(vil_ctx* ctx, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant);
+/* (the same solve with the chain's W W^T subtraction in front of it: vilsolve_debug_ww.h) */
 /* the 64 words of the kernels' debug block (DevP::dbg: the clock stamps of the -DVIL_STAMPS build, tools/probe_step.py) of the uploaded window */
 int vil_debug_read(vil_ctx* ctx, long long* out64);
 

@@ -256,9 +256,14 @@ __device__ __forceinline__ void prechain_wg(const DevP& P, const Ctl& ctl, const
     PSTAMP(16);
 }
 
+// chWW: tile g = I (I + 1) / 2 + J of W W^T in LANE-MAJOR layout, 256 doubles per tile -- the matrix cores' accumulator map: lane l of a wave holds the elements
+// (row (l >> 4) + 4 q, column l & 15), q = 0 .. 3, and finds them at g * 256 + 4 l + q: 32 contiguous, aligned bytes per lane, one dense 2 kB block per wave.  The
+// master subtracts the tile from the factorisation's register tile (same map) without passing through LDS.  Writer, reader and the test hook all go through here.
+__host__ __device__ inline int ww_idx(const int g, const int r, const int c) { return (g << 8) + ((((r & 3) << 4) + c) << 2) + (r >> 2); }
+
 // One 16 x 16 tile (I, J), J <= I, of W W^T per workgroup (its first 256 threads: the four waves split the chain columns, their
 // accumulators are added through LDS).  W^T: column j of the chain at chW[j * RS + row], rows = pose part + the right-hand-side row.
-// Output in the tiled lower layout of the step kernel (TILE_RS = 17).
+// Output in the lane-major tile layout (ww_idx).
 // FUSED: the four waves' accumulators meet in the workgroup's DYNAMIC LDS (`lds`, >= 1024 doubles) -- the one-launch iteration carries no static LDS, so
 // that its dynamic size is the larger of the sweep roles' and the step roles' needs, not their sum
 template <bool FUSED = false>
@@ -302,9 +307,10 @@ __device__ __forceinline__ void prechain_ww_tile(const DevP& P, const int tile, 
     }
     __syncthreads();
     if (act) {
-        const int r = t >> 4, c = t & 15;
-        const double v = (acc_s[0][t] + acc_s[1][t]) + (acc_s[2][t] + acc_s[3][t]);
-        st_ag(P.chWW + (size_t)tile * (16 * 17) + r * 17 + c, v);
+        // thread t sums the element that lands at tile * 256 + t (ww_idx): a wave stores 512 contiguous bytes
+        const int l = t >> 2, r = (l >> 4) + 4 * (t & 3), c = l & 15, e = (r << 4) + c;
+        const double v = (acc_s[0][e] + acc_s[1][e]) + (acc_s[2][e] + acc_s[3][e]);
+        st_ag(P.chWW + ww_idx(tile, r, c), v);
     }
 }
 

@@ -249,6 +249,9 @@ __device__ __forceinline__ int tl_phys(int e) { return (e >> 8) * TILE_SZ + ((e 
 // On return rows < D hold L, row D holds y = L^-1 rhs, s.dinv[j] = 1 / L_jj.  Returns false (uniformly) on a
 // non-positive pivot.
 struct NoPre { template <class C> __device__ __forceinline__ void operator()(C*, const int*) const {} };
+// POST (chol_lookahead / chol_rowwave): called once by every wave behind the first barrier -- the first panel runs on the panel wave(s) alone, and what the other waves
+// issue here (loads that are not needed before the factorisation ends) is off the path into it
+struct NoPost { __device__ __forceinline__ void operator()() const {} };
 // PRE: called once with the freshly loaded register tiles (REGRES) -- the chain path subtracts W W^T there
 template <bool REGRES, class PTR, class PRE = NoPre>
 __device__ __forceinline__ bool chol_blocked(PTR A, int D, StepShared& s, double* Acol = nullptr, PRE pre = PRE()) {
@@ -449,8 +452,8 @@ __device__ __forceinline__ bool chol_blocked(PTR A, int D, StepShared& s, double
 // enters it.  ONE barrier per block step, and the panel group's chain (~2000 cycles) is the step; chol_blocked needs ~3500 (diagonal block,
 // panel, barrier, trailing update, barrier, everybody in lockstep).
 // On return rows < D hold L, row D holds y = L^-1 rhs, s.dinv[j] = 1 / L_jj.  Returns false (uniformly) on a non-positive pivot.
-template <int SLOTS = CH_SLOTS, bool DIAG = true, class PTR, class PRE = NoPre>      // SLOTS: register tiles per wave (8 waves x SLOTS >= the tiles of the matrix); DIAG = false: the diagonal of L is not formed (the solves read s.dinv), its slots keep their old values
-__device__ __forceinline__ bool chol_lookahead(PTR A, int D, StepShared& s, PRE pre = PRE()) {
+template <int SLOTS = CH_SLOTS, bool DIAG = true, class PTR, class PRE = NoPre, class POST = NoPost>      // SLOTS: register tiles per wave (8 waves x SLOTS >= the tiles of the matrix); DIAG = false: the diagonal of L is not formed (the solves read s.dinv), its slots keep their old values
+__device__ __forceinline__ bool chol_lookahead(PTR A, int D, StepShared& s, PRE pre = PRE(), POST post = POST()) {
     const int t = vil_tid(), NT = blockDim.x, wave = t >> 6, lane = t & 63, NW = NT >> 6;
     const int R = D + 1;                 // rows including the rhs row
     const int T = (R + 15) >> 4;         // tile rows
@@ -566,6 +569,7 @@ __device__ __forceinline__ bool chol_lookahead(PTR A, int D, StepShared& s, PRE 
         for (int q = 0; q < 4; ++q) A[cb + q * (4 * TILE_RS)] = Creg[u][q];
     }
     lds_barrier();
+    post();
     if (tp >= 0) { if (D >= STEP_NB) diag_panel(0, std::true_type{}, std::false_type{}); else diag_panel(0, std::false_type{}, std::false_type{}); }
     lds_barrier();
     if (!s.cok) return false;
@@ -784,8 +788,8 @@ __device__ __forceinline__ void rowwave_panel_second(PTR A, const int Kt, const 
         A[base + k] = t[k];
     }
 }
-template <int SLOTS = 3, class PTR, class PRE = NoPre>
-__device__ __forceinline__ bool chol_rowwave(PTR A, int D, StepShared& s, PRE pre = PRE()) {
+template <int SLOTS = 3, class PTR, class PRE = NoPre, class POST = NoPost>
+__device__ __forceinline__ bool chol_rowwave(PTR A, int D, StepShared& s, PRE pre = PRE(), POST post = POST()) {
     const int t = vil_tid(), NT = blockDim.x, wave = t >> 6, lane = t & 63, NW = NT >> 6;
     const int R = D + 1, T = (R + 15) >> 4, TD = (D + 15) >> 4;
     const int la = (lane & 15) * TILE_RS + (lane >> 4);     // operand element (row lane&15, k lane>>4) inside a tile
@@ -821,6 +825,7 @@ __device__ __forceinline__ bool chol_rowwave(PTR A, int D, StepShared& s, PRE pr
         for (int q = 0; q < 4; ++q) A[cb + q * (4 * TILE_RS)] = Creg[u][q];
     }
     lds_barrier();
+    post();
     auto update = [&](const int u, const int Kt) {          // tile of slot u -= X_I X_J^T over the 16 columns of tile column Kt
         const int I = tIJ[u] >> 8, J = tIJ[u] & 255;
         const int ab = tl_base(I, Kt) + la, bb = tl_base(J, Kt) + la;
@@ -858,10 +863,64 @@ __device__ __forceinline__ bool chol_rowwave(PTR A, int D, StepShared& s, PRE pr
     return s.cok != 0;
 }
 // K <= 20: the row-per-lane panels; otherwise the look-ahead factorisation
-template <int SLOTS, class PTR, class PRE = NoPre>
-__device__ __forceinline__ bool chol_dense(PTR A, int D, StepShared& s, PRE pre = PRE()) {
-    if (D >= 16 && D + 1 <= 132 && (blockDim.x >> 6) >= 8) return chol_rowwave<SLOTS>(A, D, s, pre);
-    return chol_lookahead<SLOTS, false>(A, D, s, pre);
+template <int SLOTS, class PTR, class PRE = NoPre, class POST = NoPost>
+__device__ __forceinline__ bool chol_dense(PTR A, int D, StepShared& s, PRE pre = PRE(), POST post = POST()) {
+    if (D >= 16 && D + 1 <= 132 && (blockDim.x >> 6) >= 8) return chol_rowwave<SLOTS>(A, D, s, pre, post);
+    return chol_lookahead<SLOTS, false>(A, D, s, pre, post);
+}
+
+// ---- M_pp -= Sc (W W^T) Sc on the factorisation's register tiles (a PRE functor's two halves).  A tile of chWW (ww_idx, vil_prechain.hpp) and a register tile share
+//      the lane-to-element map: a lane's four operands are chWW[g * 256 + 4 lane + q], its elements (i, j) = (16 I + (lane >> 4) + 4 q, 16 J + (lane & 15)).
+//      ww_tiles_load issues the loads of the wave's slots (empty slots: a scalar branch, nothing is loaded); ww_tiles_sub forms
+//          C -= (i < NP ? sc[i] : 1) * ww * sc[j]        as one product, then one fma -- what the read-modify-write of the LDS tiles compiled to, bit for bit
+//      on the elements i <= NP, j <= i, j < NP (the rhs row is scaled by its column only; the diagonal tiles' upper triangles, the rhs column and the padding
+//      rows keep what they hold, whatever chWW holds there: operands are loaded unconditionally and the RESULT is selected).
+template <int SLOTS>
+__device__ __forceinline__ void ww_tiles_load(const double* chWW, const int* tIJ, const int lane, double (&ww)[SLOTS][4]) {
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+        const int ij = __builtin_amdgcn_readfirstlane(tIJ[u]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ww[u][q] = 0.0;
+        if (ij < 0) continue;
+        const double* p = chWW + ww_idx(tri_off(ij >> 8) + (ij & 255), 0, 0) + 4 * lane;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ww[u][q] = ld_ag(p + q);
+    }
+}
+template <int SLOTS>
+__device__ __forceinline__ void ww_tiles_sub(d4* Creg, const int* tIJ, const int lane, const double (&ww)[SLOTS][4], const double* sc, const int NP) {
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+        const int ij = __builtin_amdgcn_readfirstlane(tIJ[u]);
+        if (ij < 0) continue;
+        const int i0 = ((ij >> 8) << 4) + (lane >> 4), j = ((ij & 255) << 4) + (lane & 15);
+        const double b = sc[min(j, NP - 1)];
+        double a[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = sc[min(i0 + 4 * q, NP - 1)];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = i0 + 4 * q;
+            const double p = (i < NP ? a[q] : 1.0) * ww[u][q];
+            const double r = __builtin_fma(-p, b, Creg[u][q]);
+            Creg[u][q] = (i <= NP && j <= i && j < NP) ? r : Creg[u][q];
+        }
+    }
+}
+// gather + step in one launch: a wave waits for the tile workgroups of ITS slots only (lane u polls slot u's flag; a wave without tiles polls the first tile's: any
+// tile's flag implies the chain workgroup's).  No barrier behind it: nothing a wave loads of what those workgroups wrote is requested before the wave is through here.
+template <int SLOTS>
+__device__ __forceinline__ void ww_tiles_wait(const int* wwflag, const int* tIJ, const int lane, const int epoch, int* abortf) {
+    int gl = -1; bool any = false;
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+        const int ij = __builtin_amdgcn_readfirstlane(tIJ[u]);
+        if (ij >= 0) { any = true; if (lane == u) gl = tri_off(ij >> 8) + (ij & 255); }
+    }
+    if (!any && lane == 0) gl = 0;
+    if (gl >= 0) spin_until_eq(wwflag + gl, epoch, abortf);
+    asm volatile("" ::: "memory");
 }
 
 // back substitution L^T x = y, a COLUMN per lane: the counterpart of chol_rowwave's panels.  From the last diagonal tile up, one wave: lane (g, j) owns column j of
@@ -1219,47 +1278,44 @@ __device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, 
             }
         }
     }
-    if (P.rs_merged) {   // the chain workgroup and the W W^T tile workgroups of this launch are done (a tile's flag implies the chain's)
-        for (int i = t; i < P.n_ww; i += VIL_STEP_THREADS) spin_until_eq(P.wwflag + i, epoch, P.abortf);
-        __syncthreads();                               // (everything they left is read at agent scope below: no fence)
-    }
-    if (t == 0) prof_stamp(P, epoch - 1, 9);
-    SSTAMP(1);
+    __syncthreads();                                   // the packed tiles are in LDS: the factorisation loads its register tiles from them
+    // ---- M_pp -= Sc (W W^T) Sc on the factorisation's register tiles, as its PRE functor (ww_tiles_*).  Everything the chain and tile workgroups of this launch left is
+    //      requested in here, by each wave behind the flags of its OWN tiles (gather + step in one launch; otherwise an earlier launch wrote it): the tiles of
+    //      chWW, the chain share of u^T S' u, the chain's status, its last flag and the prefetch of W^T.  No workgroup barrier and no LDS pass in between.
     // (the chain workgroup's last flag -- factors for the chain back substitution, written ~4 us after W -- rides in the round trip of the W W^T loads:
     //  a thread that sees it posted here needs neither a poll nor a barrier after the dense part)
-    const int f2 = (P.rs_merged || P.prechain == 2) ? ld_ag(P.chflag + 2) : 0;
-    {   // M_pp -= Sc (W W^T) Sc: each thread on the very elements it packed (same index map: no barrier in between)
-        const int NE = ntile << 8;
-        for (int e0 = t; e0 < NE; e0 += 8 * VIL_STEP_THREADS) {
-            double ww[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) ww[u] = ld_ag(P.chWW + tl_phys(min(e0 + VIL_STEP_THREADS * u, NE - 1)));
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e = e0 + VIL_STEP_THREADS * u;
-                if (e >= NE) break;
-                const int tile = e >> 8, w = e & 255, i = (s.tI[tile] << 4) + (w >> 4), j = (s.tJ[tile] << 4) + (w & 15);
-                if (i <= NP && j <= i && j < NP) Tl[tl_phys(e)] -= (i < NP ? s.sc[i] : 1.0) * ww[u] * s.sc[j];
-            }
-        }
-        // chain share of u^T S' u: chain x chain + 2 u_p . (S'_pb u_b)
-        if (t < NP) qpart += 2.0 * s.y[t] * (ld_ag(P.chZ + t) + ld_ag(P.chZ + R + t));
-        if (t == 0) qpart += ld_ag(P.chQ) + ld_ag(P.chQ + 1);
-        if (t == 0 && !ld_ag(P.chOk)) s.ok = 0;
-    }
-    __syncthreads();
-    SSTAMP(2); SSTAMP(3);
-    if (!s.ok) return false;
-    // W^T for the chain back substitution (t = y_b - W^T x_p) does not depend on x_p: its loads are issued here and land under the first block steps of the
-    // factorisation, whose barriers order LDS only (lds_barrier) and do not wait for them
+    // (W^T for the chain back substitution (t = y_b - W^T x_p) does not depend on x_p: its loads are issued behind the factorisation's first barrier (`prefetch`
+    //  below) and land under its first block steps, whose barriers order LDS only (lds_barrier) and do not wait for them)
     const int G = (4 * NB <= VIL_STEP_THREADS) ? 4 : 2;
     const int j = t / G, part = t - j * G;
     const int jc = min(j, NB - 1);
     double wv[24], wrhs = 0.0;
+    int f2 = 0;
     const bool small = ntile <= 24;                    // K <= 12: three register tiles per wave in the factorisation instead of seven -- room for the prefetch
-    if (small) {
-        // (waves whose threads all sit past the last chain column -- the last two at K = 10, the panel wave of the factorisation among them -- ask for nothing: their 25
-        //  requests per lane queued in front of the factorisation's first panel at the compute unit's 5 lanes per ns)
+    auto wwsub = [&](auto slots_c, d4* Creg, const int* tIJ) {
+        constexpr int SL = decltype(slots_c)::value;
+        const int lane = t & 63;
+        if (P.rs_merged) ww_tiles_wait<SL>(P.wwflag, tIJ, lane, epoch, P.abortf);
+        if (t == 0) prof_stamp(P, epoch - 1, 9);
+        SSTAMP(1);
+        double ww[SL][4];
+        ww_tiles_load<SL>(P.chWW, tIJ, lane, ww);
+        f2 = (P.rs_merged || P.prechain == 2) ? ld_ag(P.chflag + 2) : 0;
+        // chain share of u^T S' u: chain x chain + 2 u_p . (S'_pb u_b)
+        double z0 = 0.0, z1 = 0.0, q0 = 0.0, q1 = 0.0; int cok = 1;
+        if (t < NP) { z0 = ld_ag(P.chZ + t); z1 = ld_ag(P.chZ + R + t); }
+        if (t == 0) { q0 = ld_ag(P.chQ); q1 = ld_ag(P.chQ + 1); cok = ld_ag(P.chOk); }
+        ww_tiles_sub<SL>(Creg, tIJ, lane, ww, s.sc, NP);
+        if (t < NP) qpart += 2.0 * s.y[t] * (z0 + z1);
+        if (t == 0) qpart += q0 + q1;
+        if (t == 0 && !cok) s.ok = 0;                  // (looked at behind the factorisation: its first barrier orders this store; factoring garbage once is harmless)
+        SSTAMP(2); SSTAMP(3);
+    };
+    // the prefetch of W^T, behind the factorisation's first barrier (its POST functor; every wave has been through wwsub: W^T is complete).  1536 + 64 requests per
+    // wave are 1.9 us of the compute unit's load issue: in front of the barrier they were 1.9 us of the path into the first panel, behind it they run while the
+    // panel wave factors the first tile column and the tile waves have nothing to do
+    auto prefetch = [&]() {
+        // (waves whose threads all sit past the last chain column -- the last two at K = 10, the panel wave of the factorisation among them -- ask for nothing)
         const bool wave_has_columns = __builtin_amdgcn_readfirstlane(((t >> 6) << 6) / G) < NB;      // (a scalar branch)
 #pragma unroll
         for (int q = 0; q < 24; ++q) wv[q] = 0.0;
@@ -1268,8 +1324,16 @@ __device__ __forceinline__ bool solve_prechain(const DevP& P, const SysBuf& sb, 
             for (int q = 0; q < 24; ++q) wv[q] = ld_ag(Wt + (size_t)jc * RS + min(part + q * G, NP - 1));
             wrhs = ld_ag(Wt + (size_t)jc * RS + NP);
         }
-        if (!(RW ? chol_dense<3>(Tl, NP, s) : chol_lookahead<3, false>(Tl, NP, s))) return false;
-    } else if (!(RW ? chol_dense<CH_SLOTS>(Tl, NP, s) : chol_lookahead<CH_SLOTS, false>(Tl, NP, s))) return false;
+    };
+    bool cf;
+    if (small) {
+        auto pre = [&](d4* Creg, const int* tIJ) { wwsub(std::integral_constant<int, 3>{}, Creg, tIJ); };
+        cf = RW ? chol_dense<3>(Tl, NP, s, pre, prefetch) : chol_lookahead<3, false>(Tl, NP, s, pre, prefetch);
+    } else {
+        auto pre = [&](d4* Creg, const int* tIJ) { wwsub(std::integral_constant<int, CH_SLOTS>{}, Creg, tIJ); };
+        cf = RW ? chol_dense<CH_SLOTS>(Tl, NP, s, pre) : chol_lookahead<CH_SLOTS, false>(Tl, NP, s, pre);
+    }
+    if (!cf || !s.ok) return false;
     SSTAMP(4);
     if (t == 0) prof_stamp(P, epoch - 1, 10);
     if (RW) back_subst_cols(Tl, NP, s); else back_subst(Tl, NP, s);

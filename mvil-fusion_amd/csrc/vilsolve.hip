@@ -17,6 +17,7 @@
 #include <map>
 
 #include "../../include/vilsolve_debug.h"
+#include "../../include/vilsolve_debug_ww.h"
 #include "vil_internal.h"
 #include "vil_comm.hpp"
 #include "vil_resident.hpp"
@@ -212,17 +213,37 @@ static void quat_to_R_host(const double* q, double* R) {
 
 // test hook (vil_debug_dense_solve): the step's dense factorisation + back substitution on a matrix of the caller's -- one workgroup, the tiled LDS layout of vil_step.hpp.
 // RW: what the one-launch iteration runs (chol_dense / back_subst_cols); otherwise the look-ahead factorisation and the back substitution with inverted diagonal tiles.
-template <int SLOTS, bool RW>
-__global__ __launch_bounds__(VIL_STEP_THREADS) void k_debug_dense(const double* Ain /* (D+1) x (D+1) row major: lower triangle, last row = right-hand side */, double* Lout, double* xout, int* okout, int D) {
+// WWS (vil_debug_dense_solve_ww): the matrix is A - S WW S, subtracted the way the step subtracts the chain's W W^T -- on the factorisation's register tiles, out of
+// chWW in the lane-major tile layout (k_debug_ww_fill wrote it through ww_idx), with the scales sc (rhs row: its column's scale only).
+__global__ void k_debug_ww_fill(const double* WW /* (D+1) x (D+1) row major, every entry as it stands */, double* chWW, int D, double pad /* tile elements past row / column D */) {
+    const int R = D + 1, T = (R + 15) >> 4, n = ((T * (T + 1)) >> 1) << 8;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+        const int g = e >> 8, r = (e >> 4) & 15, c = e & 15;
+        int I = 0; while ((I + 1) * (I + 2) / 2 <= g) ++I;
+        const int J = g - I * (I + 1) / 2, i = (I << 4) + r, j = (J << 4) + c;
+        chWW[vd::ww_idx(g, r, c)] = (i < R && j < R) ? WW[(size_t)i * R + j] : pad;
+    }
+}
+template <int SLOTS, bool RW, bool WWS = false>
+__global__ __launch_bounds__(VIL_STEP_THREADS) void k_debug_dense(const double* Ain /* (D+1) x (D+1) row major: lower triangle, last row = right-hand side */, double* Lout, double* xout, int* okout, int D, const double* chWW = nullptr, const double* scin = nullptr) {
     extern __shared__ double dbgA[];
     __shared__ vd::StepShared s;
     const int t = threadIdx.x, R = D + 1, T = (R + 15) >> 4, NTL = ((T * (T + 1)) >> 1) * TILE_SZ;
     if (t == 0) { int g = 0; for (int I = 0; I < T; ++I) for (int J = 0; J <= I; ++J) { s.tI[g] = (unsigned char)I; s.tJ[g] = (unsigned char)J; ++g; } }
     for (int e = t; e < NTL; e += blockDim.x) dbgA[e] = 0.0;
+    if constexpr (WWS) { for (int e = t; e < D; e += blockDim.x) s.sc[e] = scin[e]; }
     __syncthreads();
     for (int e = t; e < R * R; e += blockDim.x) { const int i = e / R, j = e - i * R; if (j <= i && j < D) dbgA[vd::tl_idx(i, j)] = Ain[e]; }
     __syncthreads();
     bool ok;
+    if constexpr (WWS) {
+        auto pre = [&](vd::d4* Creg, const int* tIJ) {
+            double ww[SLOTS][4];
+            vd::ww_tiles_load<SLOTS>(chWW, tIJ, t & 63, ww);
+            vd::ww_tiles_sub<SLOTS>(Creg, tIJ, t & 63, ww, s.sc, D);
+        };
+        if constexpr (RW) ok = vd::chol_dense<SLOTS>(dbgA, D, s, pre); else ok = vd::chol_lookahead<SLOTS, false>(dbgA, D, s, pre);
+    } else
     if constexpr (RW) ok = vd::chol_dense<SLOTS>(dbgA, D, s); else ok = vd::chol_lookahead<SLOTS, false>(dbgA, D, s);
     __syncthreads();
     for (int e = t; e < R * R; e += blockDim.x) { const int i = e / R, j = e - i * R; Lout[e] = (j < i && j < D) ? dbgA[vd::tl_idx(i, j)] : ((j == i && i < D) ? 1.0 / s.dinv[i] : 0.0); }
@@ -2220,25 +2241,40 @@ int vil_debug_drop_flag(vil_ctx* c, int32_t role, int32_t launch) {
 }
 int vil_debug_set_split(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->force_split = on != 0; c->invalidate(); return VIL_OK; }
 int vil_debug_set_slim_emul(vil_ctx* c, int32_t on) { if (!c) return VIL_ERR_INVALID_ARGUMENT; c->comm.slim_emul = on != 0; return VIL_OK; }
-int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) {
+// WW != null: the matrix is A - S WW S, subtracted on the factorisation's register tiles out of the lane-major tile layout (vil_debug_dense_solve_ww)
+static int debug_dense_run(vil_ctx* c, int32_t D, const double* A, const double* WW, const double* sc, double pad, double* L, double* x, int32_t* ok, int32_t variant) {
     if (!c || !A || !L || !x || !ok || D < 1 || D > 159 || variant < 0 || variant > 1) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
     const int R = D + 1, T = (R + 15) / 16, nt = T * (T + 1) / 2;
     const size_t lds = 8 * (size_t)TILE_SZ * nt, nb = 8 * (size_t)R * R;
-    double *dA = nullptr, *dL = nullptr, *dx = nullptr; int* dok = nullptr;
+    double *dA = nullptr, *dL = nullptr, *dx = nullptr, *dW = nullptr, *dWW = nullptr, *dsc = nullptr; int* dok = nullptr;
     HIPCHK(hipMalloc((void**)&dA, nb)); HIPCHK(hipMalloc((void**)&dL, nb)); HIPCHK(hipMalloc((void**)&dx, 8 * (size_t)R)); HIPCHK(hipMalloc((void**)&dok, 64));
     HIPCHK(hipMemcpy(dA, A, nb, hipMemcpyHostToDevice));
-    const bool small = nt <= 18;                         // (three register tiles per tile wave are enough -- what the step takes at K <= 10)
-    const void* fn = variant ? (small ? (const void*)k_debug_dense<3, true> : (const void*)k_debug_dense<CH_SLOTS, true>) : (small ? (const void*)k_debug_dense<3, false> : (const void*)k_debug_dense<CH_SLOTS, false>);
+    const void* fn;
+    if (WW) {
+        HIPCHK(hipMalloc((void**)&dW, nb)); HIPCHK(hipMalloc((void**)&dWW, 8 * (size_t)256 * nt)); HIPCHK(hipMalloc((void**)&dsc, 8 * (size_t)D));
+        HIPCHK(hipMemcpy(dW, WW, nb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dsc, sc, 8 * (size_t)D, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_debug_ww_fill, dim3(nt), dim3(256), 0, c->stream, dW, dWW, D, pad);
+        const bool small = nt <= 24;                     // (the step's own choice: solve_prechain)
+        fn = variant ? (small ? (const void*)k_debug_dense<3, true, true> : (const void*)k_debug_dense<CH_SLOTS, true, true>) : (small ? (const void*)k_debug_dense<3, false, true> : (const void*)k_debug_dense<CH_SLOTS, false, true>);
+    } else {
+        const bool small = nt <= 18;                     // (three register tiles per tile wave are enough -- what the step takes at K <= 10)
+        fn = variant ? (small ? (const void*)k_debug_dense<3, true> : (const void*)k_debug_dense<CH_SLOTS, true>) : (small ? (const void*)k_debug_dense<3, false> : (const void*)k_debug_dense<CH_SLOTS, false>);
+    }
     HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* args[] = {(void*)&dA, (void*)&dL, (void*)&dx, (void*)&dok, (void*)&D};
+    void* args[] = {(void*)&dA, (void*)&dL, (void*)&dx, (void*)&dok, (void*)&D, (void*)&dWW, (void*)&dsc};
     HIPCHK(hipLaunchKernel(fn, dim3(1), dim3(VIL_STEP_THREADS), args, lds, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     int hok = 0;
     HIPCHK(hipMemcpy(L, dL, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(x, dx, 8 * (size_t)D, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hok, dok, 4, hipMemcpyDeviceToHost));
     *ok = hok;
-    hipFree(dA); hipFree(dL); hipFree(dx); hipFree(dok);
+    hipFree(dA); hipFree(dL); hipFree(dx); hipFree(dok); hipFree(dW); hipFree(dWW); hipFree(dsc);
     return VIL_OK;
+}
+int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) { return debug_dense_run(c, D, A, nullptr, nullptr, 0.0, L, x, ok, variant); }
+int vil_debug_dense_solve_ww(vil_ctx* c, int32_t D, const double* A, const double* WW, const double* sc, double pad, double* L, double* x, int32_t* ok, int32_t variant) {
+    if (!WW || !sc) return VIL_ERR_INVALID_ARGUMENT;
+    return debug_dense_run(c, D, A, WW, sc, pad, L, x, ok, variant);
 }
 int vil_debug_read(vil_ctx* c, long long* out64) {
     if (!c || !c->uploaded) return VIL_ERR_INVALID_ARGUMENT;
