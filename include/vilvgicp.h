@@ -49,12 +49,15 @@ void vgicp_destroy(vgicp_ctx* ctx);
 void vgicp_default_options(vgicp_options* o);
 /* target cloud + covariances -> Gaussian voxel map of edge `resolution` (estimator.cpp:271 uses 0.5).  Both builders (vilvgicp_voxel.h)
  * build the map aside and install it when it is complete: after any failure -- VIL_ERR_NON_FINITE, or VIL_ERR_DEVICE for a failed
- * allocation or copy -- the previous target stays usable and unchanged. */
+ * allocation or copy -- the previous target stays usable and unchanged.
+ * The map keys a voxel with 21 bits per axis: the target must lie within 2^20 voxels of the origin on every axis, and a transformed source
+ * point whose voxel coordinate (or that of a DIRECT7 / DIRECT27 neighbour) is outside [-2^20, 2^20) has no correspondence. */
 int vgicp_set_target(vgicp_ctx* ctx, int32_t n, const float* xyz, const double* cov9, double resolution);
 int vgicp_set_source(vgicp_ctx* ctx, int32_t n, const float* xyz, const double* cov9);
 /* Covariance of the k nearest neighbours of every point (the point itself included, as pcl's nearestKSearch returns it),
  * regularised like RegularizationMethod::PLANE: singular values replaced by (1, 1, 1e-3).  The reference finds the
  * neighbours with a kd-tree in float; this is an EXACT search with the same float distances (ties may order differently).
+ * For an all-zero covariance (k coincident points) the reference's JacobiSVD returns diag(1, 1, 1e-3); this library returns diag(1e-3, 1, 1).
  * out_cov9: n x 9 host buffer. */
 int vgicp_covariances(vgicp_ctx* ctx, int32_t n, const float* xyz, int32_t k, double* out_cov9);
 /* neighbour search of vgicp_covariances: clouds of at least min_points points (default 4096) use the uniform-grid search with an initial

@@ -36,7 +36,7 @@ __device__ __forceinline__ float sqdist_nofma(float qx, float qy, float qz, floa
 }
 // The intrinsics above are plain operators in the compiler's HIP headers, defined with contraction allowed, so the back end may still fuse
 // them (it does in places).  The same sum with contraction switched off where the operations are written: never an fma.  Rows that
-// promise the CPU's bits (villoop.hip, vilmap.hip) search with STRICT = true below; the others keep the code they were measured and pinned with.
+// promise the CPU's bits (villoop.hip, vilmap.hip, vilvgicp.hip) search with STRICT = true below; the others keep the code they were measured and pinned with.
 __device__ __forceinline__ float sqdist_strict(float qx, float qy, float qz, float x, float y, float z) {
 #pragma clang fp contract(off)
     const float dx = qx - x, dy = qy - y, dz = qz - z;

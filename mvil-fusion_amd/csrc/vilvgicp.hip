@@ -41,9 +41,19 @@ using vknn::pack_key; using vknn::hash_key;
 
 __device__ __forceinline__ double wave_sum64(double v) { return vd::wave_total(v); }   // DPP rotate-and-add, no LDS round trips
 
+// 1 / x without the IEEE divide (a 1 k-cycle chain in the middle of every slot): the hardware seed and two Newton steps in residual form,
+// y += y (1 - x y) with both products fused, so the last step rounds once -- under one ulp.  vd::rcp_nr's y (2 - x y) rounds the factor and
+// then the product (1-2 ulp), and every slot of a voxel repeats that error with the same sign: tests/test_gpu_vgicp_ref.py saw it in the
+// sum (edges, res 0.1: 1.9 ulp of the error against the float64 routes' 0.1).  Same instruction count.
+__device__ __forceinline__ double rcp_res(double x) {
+    double y = __builtin_amdgcn_rcp(x);
+    y = fma(y, fma(-x, y, 1.0), y);
+    y = fma(y, fma(-x, y, 1.0), y);
+    return y;
+}
 __device__ __forceinline__ void inv3(const double* a, double* o) {
     const double c0 = a[4] * a[8] - a[5] * a[7], c1 = a[5] * a[6] - a[3] * a[8], c2 = a[3] * a[7] - a[4] * a[6];
-    const double id = vd::rcp_nr(a[0] * c0 + a[1] * c1 + a[2] * c2);      // (1-2 ulp; the IEEE divide is a 1 k-cycle chain in the middle of every slot)
+    const double id = rcp_res(a[0] * c0 + a[1] * c1 + a[2] * c2);
     o[0] = c0 * id; o[1] = (a[2] * a[7] - a[1] * a[8]) * id; o[2] = (a[1] * a[5] - a[2] * a[4]) * id;
     o[3] = c1 * id; o[4] = (a[0] * a[8] - a[2] * a[6]) * id; o[5] = (a[2] * a[3] - a[0] * a[5]) * id;
     o[6] = c2 * id; o[7] = (a[1] * a[6] - a[0] * a[7]) * id; o[8] = (a[0] * a[4] - a[1] * a[3]) * id;
@@ -89,7 +99,11 @@ __device__ __forceinline__ void vgicp_lin_slot(int tid, int noff, const float* _
         int kx = vox_coord(tx, res, ires), ky = vox_coord(ty, res, ires), kz = vox_coord(tz, res, ires);
         if (noff == 7) { const int d = (o + 1) >> 1, s = (o & 1) ? 1 : -1; if (o) { if (d == 1) kx += s; else if (d == 2) ky += s; else kz += s; } }   // (0) (+x -x) (+y -y) (+z -z)
         else if (noff == 27) { kx += o / 9 - 1; ky += (o / 3) % 3 - 1; kz += o % 3 - 1; }
-        const long long key = pack_key(kx, ky, kz);
+        // pack_key keeps 21 bits per axis: a coordinate outside [-2^20, 2^20) would alias a voxel 2^21 cells away, where the reference's
+        // Eigen::Vector3i key finds nothing.  Such a slot probes for a key no voxel has (stored keys are >= 0, empty slots -1) and ends at the
+        // first empty slot; the probe loop itself is unchanged
+        const bool in_range = ((((unsigned)kx + (1u << 20)) | ((unsigned)ky + (1u << 20)) | ((unsigned)kz + (1u << 20))) >> 21) == 0u;
+        const long long key = in_range ? pack_key(kx, ky, kz) : -2LL;
         // the source covariance does not depend on the probe: its loads go out before the dependent chain key -> voxel -> mean / cov
         double ca[9];
 #pragma unroll
@@ -191,8 +205,8 @@ __global__ __launch_bounds__(VG_THREADS) void k_vgicp_sum(int nblk, const double
 // FastGICP::calculate_covariances (fast_gicp_impl.hpp:241-300), k <= 20, RegularizationMethod::PLANE.
 // Exact k-nearest-neighbour search by tiles: thread = query point, the candidate points stream through LDS 256 at a time,
 // the running k best (float squared distance, index) live in registers as a sorted list updated by an unrolled,
-// branch-free insertion (static register indices: no scratch).  Same float arithmetic and tie order (smaller index
-// first) as the oracle, so both select the same neighbours.  Then mean / covariance in fp64 and
+// branch-free insertion (static register indices: no scratch).  The float distance is the unfused sum (sqdist_strict) and ties go to the
+// smaller index: the neighbours are those of tests/vgicp_ref.py, whatever order the candidates arrive in.  Then mean / covariance in fp64 and
 // U diag(1, 1, 1e-3) V^T = I - (1 - 1e-3) n n^T with n the eigenvector of the smallest eigenvalue (cyclic Jacobi, 3 x 3).
 using namespace vknn;
 
@@ -254,7 +268,7 @@ __global__ __launch_bounds__(VG_THREADS) void k_knn_cov(int n, const float* __re
         if (j0 < n) { sx[threadIdx.x] = xyz[3 * j0]; sy[threadIdx.x] = xyz[3 * j0 + 1]; sz[threadIdx.x] = xyz[3 * j0 + 2]; }
         __syncthreads();
         const int cnt = min(VG_THREADS, n - t0);
-        for (int jj = 0; jj < cnt; ++jj) knn_insert(L, sqdist_nofma(qx, qy, qz, sx[jj], sy[jj], sz[jj]), t0 + jj);
+        for (int jj = 0; jj < cnt; ++jj) knn_insert(L, sqdist_strict(qx, qy, qz, sx[jj], sy[jj], sz[jj]), t0 + jj);      // never an fma: the header promises the reference's float distances (vil_knn.hpp)
     }
     if (live) knn_plane_cov(L, xyz, k, cov9 + (size_t)9 * i);
 }
@@ -268,7 +282,7 @@ __global__ __launch_bounds__(64 * VG_QPB) void k_knn_wave(int n, const float* __
     const int pos = blockIdx.x * VG_QPB + wave;                              // queries in cell order: neighbouring waves share cells in L2
     if (pos >= n) return;
     unsigned long long best;
-    knn_wave_query(best, cxyz[3 * pos], cxyz[3 * pos + 1], cxyz[3 * pos + 2], min(k, n), n, G, order, cxyz, wl_all + wave * KNN_WL_CAP, 3.0e38f, 1);
+    knn_wave_query<true>(best, cxyz[3 * pos], cxyz[3 * pos + 1], cxyz[3 * pos + 2], min(k, n), n, G, order, cxyz, wl_all + wave * KNN_WL_CAP, 3.0e38f, 1);
     if (lane < KNN_MAX) nn[(size_t)KNN_MAX * order[pos] + lane] = lane < min(k, n) ? (int)(unsigned)best : 0x7fffffff;
 }
 __global__ __launch_bounds__(VG_THREADS) void k_knn_fit(int n, const float* __restrict__ xyz, const int* __restrict__ nn, int k, double* __restrict__ cov9) {

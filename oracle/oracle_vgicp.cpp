@@ -68,7 +68,10 @@ void update_correspondences(Ctx& c, const double* T, int mode) {
         for (int r = 0; r < 3; ++r) ta[r] = T[4 * r] * a[0] + T[4 * r + 1] * a[1] + T[4 * r + 2] * a[2] + T[4 * r + 3];
         const Key k = voxel_coord(ta, c.res);
         for (const Key& o : off) {
-            auto it = c.vox.find({k.x + o.x, k.y + o.y, k.z + o.z});
+            const Key q = {k.x + o.x, k.y + o.y, k.z + o.z};
+            auto inside = [](int v) { return v >= -(1 << 20) && v < (1 << 20); };      // the library's limit (vilvgicp.h): 2^20 voxels from the origin per axis
+            if (!inside(q.x) || !inside(q.y) || !inside(q.z)) continue;
+            auto it = c.vox.find(q);
             if (it == c.vox.end()) continue;
             Corr cr; cr.src = i; cr.vox = &it->second;
             const double* ca = &c.scov[9 * i];

@@ -1,6 +1,8 @@
 """Pins of the CPU restatement of fast_gicp's voxelised GICP (oracle/oracle_vgicp.cpp): voxel map against a numpy
 re-derivation, b = half the gradient of the error at fixed correspondences (finite differences with the reference's
-left-multiplicative so3_exp update), H = Gauss-Newton matrix of the same error, and the LM loop recovers the relative pose."""
+left-multiplicative so3_exp update), H = Gauss-Newton matrix of the same error, and the LM loop recovers the relative pose.
+The DIRECT1 numpy loop below is a coarse pin; the independent reference of this row is the 50-digit restatement tests/vgicp_ref.py, which
+tests/test_vgicp_ref.py holds the oracle to on every fixture of tests/vgicp_fixtures.py (docs/vgicp.md)."""
 import numpy as np
 import pytest
 
