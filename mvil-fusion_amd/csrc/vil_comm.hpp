@@ -55,5 +55,5 @@ private:
     std::shared_ptr<LocalComm> local;      // in-process communicator (vil_comm_init_local)
     std::shared_ptr<IpcComm> ipc;          // multi-process peer-buffer exchange (vil_comm_ipc_export / vil_comm_ipc_init)
     vilhost::Grown<double> tmp, slim_buf;  // result of an in-place in-process sum; staging of the packed per-iteration message
-    double* agree_h = nullptr; double* agree_d = nullptr;      // agree(): 64 doubles each, pinned / device (RCCL and peer buffers)
+    vilhost::Grown<double, true> agree_h; vilhost::Grown<double> agree_d;      // agree(): 64 doubles each, pinned / device (RCCL and peer buffers)
 };

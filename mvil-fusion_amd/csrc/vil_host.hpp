@@ -1,7 +1,8 @@
 // vil_host.hpp -- the host scaffold shared by the row libraries (vilmap.hip, vilvgicp.hip, vilpreint.hip, vilscan.hip, vildepth.hip,
-// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip; through vil_voxmap.hpp, vil_knn.hpp and
-// vil_comm.hpp also their headers): one check macro, the arena layout, the owner of a row's stream / arena / pinned buffers, the kernel-event profilers,
-// the grow-only buffer (Grown), the mapped pinned record (Mapped) and the poll of a word in it (await_word).
+// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip; through vil_voxmap.hpp and vil_knn.hpp
+// also their headers) and, through vil_comm.hpp and vil_resident.hpp, by the solver itself (vilsolve.hip, vilwindow.hip, vilcomm.hip): one check macro, the
+// arena layout, the owner of a row's stream / arena / pinned buffers, the kernel-event profilers, the grow-only buffer (Grown), the mapped pinned record
+// (Mapped), the poll of a word in it (await_word) and the event behind a staging copy (Fence).  Everything the solver's context allocates is one of these.
 // Header-only, internal linkage or hidden: libvilsolve.so exports nothing from here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +59,25 @@ struct __attribute__((visibility("hidden"))) Mapped {
         return e;
     }
     void release() { if (h) hipHostFree(h); h = nullptr; d = nullptr; }
+};
+
+// An event that says a stream has passed a point (an asynchronous copy has left its pinned block): created on the first record(),
+// wait() blocks the host only while a record() is outstanding.  Both return the HIP error for the caller's check, like Profiler::mark.
+struct __attribute__((visibility("hidden"))) Fence {
+    hipEvent_t ev = nullptr; bool pending = false;         // (ev: for a hipStreamWaitEvent of the caller's)
+    Fence() = default;
+    Fence(const Fence&) = delete; Fence& operator=(const Fence&) = delete;
+    ~Fence() { if (ev) hipEventDestroy(ev); }
+    hipError_t wait() {
+        const hipError_t e = pending ? hipEventSynchronize(ev) : hipSuccess;
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+    hipError_t record(hipStream_t stream) {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess && (e = hipEventRecord(ev, stream)) == hipSuccess) pending = true;
+        return e;
+    }
 };
 
 namespace {

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "vil_host.hpp"
 #include "vil_internal.h"
 #include "vil_dev.hpp"
 
@@ -24,12 +25,11 @@ struct WinSlots {
 
 // One pushed frame travels as ONE DMA out of a pinned block into its device twin (both grow-only): fill h after begin(), then send()
 struct __attribute__((visibility("hidden"))) FrameStage {
-    char* h = nullptr; char* d = nullptr;
+    vilhost::Grown<char, true> h; vilhost::Grown<char> d;
     int begin(hipStream_t stream, size_t bytes, size_t grow_to);      // the previous frame's DMA has left the pinned block; room for `bytes` (a new pair of grow_to bytes otherwise)
     int send(hipStream_t stream, size_t bytes);
-    void release();
 private:
-    size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false;
+    vilhost::Fence sent;
 };
 
 struct __attribute__((visibility("hidden"))) LidarSlabs {
@@ -43,13 +43,12 @@ struct __attribute__((visibility("hidden"))) LidarSlabs {
     // the newest frame's points (point-major rows); of a sharded window (world > 1) this rank keeps its contiguous slice.  tables_moved: capacity grew,
     // the live slabs were copied into new tables -- a resident problem holds pointers / strides of the old ones
     int push(hipStream_t stream, int rank, int world, int n_plane, const double* plane, int n_edge, const double* edge, bool* tables_moved);
-    void release();                                                     // THE teardown
 private:
     struct Slab { int np, ne, slot; int np_all, ne_all; };      // np_all / ne_all: the frame's points BEFORE a communicator's slicing (the same on every rank)
     std::vector<Slab> slabs;       // window order
     std::vector<int> free_slots;
     int cap_p = 0, cap_e = 0, nslot = 0;      // points per slab (capacity), physical slabs
-    double* d_pl = nullptr; double* d_ed = nullptr;       // component-major: row q of the plane table at d_pl + q * nslot * cap_p
+    vilhost::Grown<double> d_pl, d_ed;                    // component-major: row q of the plane table at d_pl.p + q * nslot * cap_p
     FrameStage stage;              // AoS rows of one pushed frame
 };
 
@@ -69,24 +68,23 @@ struct __attribute__((visibility("hidden"))) Window {
     int commit_prior(hipStream_t stream, int K, bool old_, int n, int m, int nblk, const int* kind, const int* index, const int* col, const double* J0, const double* r0, const double* x);
     int prior_download(hipStream_t stream, vil_prior_out* out, int* h_word);      // returns the sticky status word
     int prior_set(hipStream_t stream, const vil_prior* pr);             // nullptr / n <= 0: no prior
-    int* status_word() const { return d_wstat; }                        // sticky status of the asynchronous work (a covariance that is not positive definite, a prior that is not finite)
-    void release();                                                     // THE teardown
+    int* status_word() const { return d_wstat.p; }                        // sticky status of the asynchronous work (a covariance that is not positive definite, a prior that is not finite)
 private:
-    void release_tables();
+    void release_tables();                                              // (open() with other dimensions)
     int NF = 0;
     std::vector<int> fslot, islot, free_f, free_i;           // window frame -> observation slot / IMU slot; free lists
     std::vector<int> ns; std::vector<double> sum_dt;          // per IMU slot: samples held, duration of the interval
-    double* d_store = nullptr; double* d_samp = nullptr; double* d_hdr = nullptr; double* d_rec = nullptr; double* d_U = nullptr;
-    double* d_prior[2] = {nullptr, nullptr}; int cur = 0;     // prior slots: [J0 nmax^2 | r0 nmax | x0 x0max | pH nmax^2 | pg0 nmax | pc0 8]
+    vilhost::Grown<double> d_store, d_samp, d_hdr, d_rec, d_U;
+    vilhost::Grown<double> d_prior[2]; int cur = 0;               // prior slots: [J0 nmax^2 | r0 nmax | x0 x0max | pH nmax^2 | pg0 nmax | pc0 8]
     int pn = 0, pm = 0; std::vector<int> pkind, pindex, pcol;  // the current prior's block structure (host)
-    int* d_wstat = nullptr;
+    vilhost::Grown<int> d_wstat;
     int lds_commit = 0;            // dynamic LDS k_prior_commit was granted
     FrameStage stage;              // [hdr 12 | dt | acc | gyr | observations | track slots] of one pushed frame
-    double* dt(int q) const { return d_samp + (size_t)q * 7 * S; }
+    double* dt(int q) const { return d_samp.p + (size_t)q * 7 * S; }
     double* acc(int q) const { return dt(q) + S; }
     double* gyr(int q) const { return dt(q) + 4 * (size_t)S; }
-    double* pJ0(int w) const { return d_prior[w]; }
-    double* pr0(int w) const { return d_prior[w] + (size_t)nmax * nmax; }
+    double* pJ0(int w) const { return d_prior[w].p; }
+    double* pr0(int w) const { return pJ0(w) + (size_t)nmax * nmax; }
     double* px0(int w) const { return pr0(w) + nmax; }
     double* pH(int w) const { return px0(w) + x0max; }
     double* pg0(int w) const { return pH(w) + (size_t)nmax * nmax; }

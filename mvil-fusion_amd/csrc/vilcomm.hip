@@ -264,16 +264,16 @@ int Comm::sum(hipStream_t stream, const double* send, double* recv, size_t cnt, 
 int Comm::agree(hipStream_t stream, int st) {
     if (local) return local->agree(rank, st);
     if (ipc) {                                             // every rank's status in its own slot of a world-long message: the worst one wins
-        const int w = ipc->world; double* h = agree_h; for (int r = 0; r < w; ++r) h[r] = r == ipc->rank ? (double)st : 0.0;
-        if (hipMemcpyAsync(agree_d, h, 8 * (size_t)w, hipMemcpyHostToDevice, stream) != hipSuccess) return VIL_ERR_DEVICE;
-        if (ipc_sum(stream, agree_d, agree_d + 32, (size_t)w, 0, kNoSeg) != VIL_OK) return VIL_ERR_COMM;
-        if (hipMemcpyAsync(h + 32, agree_d + 32, 8 * (size_t)w, hipMemcpyDeviceToHost, stream) != hipSuccess) return VIL_ERR_DEVICE;
+        const int w = ipc->world; double* h = agree_h.p; for (int r = 0; r < w; ++r) h[r] = r == ipc->rank ? (double)st : 0.0;
+        if (hipMemcpyAsync(agree_d.p, h, 8 * (size_t)w, hipMemcpyHostToDevice, stream) != hipSuccess) return VIL_ERR_DEVICE;
+        if (ipc_sum(stream, agree_d.p, agree_d.p + 32, (size_t)w, 0, kNoSeg) != VIL_OK) return VIL_ERR_COMM;
+        if (hipMemcpyAsync(h + 32, agree_d.p + 32, 8 * (size_t)w, hipMemcpyDeviceToHost, stream) != hipSuccess) return VIL_ERR_DEVICE;
         if (hipStreamSynchronize(stream) != hipSuccess) return VIL_ERR_DEVICE;
         int worst = 0; for (int r = 0; r < w; ++r) worst = std::min(worst, (int)h[32 + r]);
         return worst;
     }
     if (rccl) {
-        int* h = (int*)agree_h; int* d = (int*)agree_d; *h = st;
+        int* h = (int*)agree_h.p; int* d = (int*)agree_d.p; *h = st;
         if (hipMemcpyAsync(d, h, sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) return VIL_ERR_DEVICE;
         if (g_rccl.AllReduce(d, d, 1, ncclInt, ncclMin, rccl, stream) != ncclSuccess) return VIL_ERR_COMM;
         if (hipMemcpyAsync(h, d, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess) return VIL_ERR_DEVICE;
@@ -297,11 +297,11 @@ void Comm::release(int device) {
     hipSetDevice(device);
     if (rccl && g_rccl.CommDestroy) g_rccl.CommDestroy(rccl);
     rccl = nullptr; local.reset();
-    if (ipc) { for (int r = 0; r < ipc->world; ++r) if (r != ipc->rank && ipc->peer_base[r]) hipIpcCloseMemHandle(ipc->peer_base[r]); if (ipc->base) hipFree(ipc->base); ipc.reset(); }
+    if (ipc) { for (int r = 0; r < ipc->world; ++r) if (r != ipc->rank && ipc->peer_base[r]) hipIpcCloseMemHandle(ipc->peer_base[r]); hipFree(ipc->base); ipc.reset(); }
     tmp.release(); slim_buf.release();
-    hipHostFree(agree_h); hipFree(agree_d); agree_h = agree_d = nullptr;
+    agree_h.release(); agree_d.release();
 }
-int Comm::alloc_agree() { HIPCHK(hipHostMalloc((void**)&agree_h, 8 * 64, hipHostMallocDefault)); HIPCHK(hipMalloc(&agree_d, 8 * 64)); return VIL_OK; }
+int Comm::alloc_agree() { HIPCHK(agree_h.reserve(64, 64)); HIPCHK(agree_d.reserve(64, 64)); return VIL_OK; }
 int Comm::unique_id(void* id128) {
     if (!g_rccl.load()) return VIL_ERR_COMM;
     ncclUniqueId id;

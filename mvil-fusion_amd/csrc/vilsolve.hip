@@ -42,22 +42,21 @@ namespace {
 // assembled in a PINNED host image and go up in one DMA; the work space (partial records, systems, step vectors) exists on the
 // device only and is cleared by a memset -- it used to travel as zeros through a pageable staging vector.
 struct Arena {
-    char* h = nullptr; size_t hcap = 0, hsize = 0;     // pinned host image of the tables
-    char* d = nullptr; size_t cap = 0;                 // device
+    vilhost::Grown<char, true> h; size_t hsize = 0;    // pinned host image of the tables
+    vilhost::Grown<char> d;                            // device
     size_t ssize = 0;                                  // work-space bytes
     bool grow(size_t need) {
-        if (need <= hcap) return true;
-        size_t ncap = hcap ? hcap : (size_t)1 << 20;
+        if (need <= h.cap) return true;
+        size_t ncap = h.cap ? h.cap : (size_t)1 << 20;
         while (ncap < need) ncap *= 2;
-        char* nh = nullptr;
-        if (hipHostMalloc((void**)&nh, ncap, hipHostMallocDefault) != hipSuccess) return false;
-        if (hsize) memcpy(nh, h, hsize);
-        if (h) hipHostFree(h);
-        h = nh; hcap = ncap;
+        vilhost::Grown<char, true> nh;                 // (reserve() keeps no contents: the image moves into a new block, the old one goes with nh)
+        if (nh.reserve(ncap, ncap) != hipSuccess) return false;
+        if (hsize) memcpy(nh.p, h.p, hsize);
+        h = std::move(nh);
         return true;
     }
     // returns (size_t)-1 when the pinned image cannot grow
-    size_t take(size_t bytes) { const size_t o = (hsize + 255) & ~size_t(255); if (!grow(o + bytes)) return (size_t)-1; if (o > hsize) memset(h + hsize, 0, o - hsize); hsize = o + bytes; return o; }
+    size_t take(size_t bytes) { const size_t o = (hsize + 255) & ~size_t(255); if (!grow(o + bytes)) return (size_t)-1; if (o > hsize) memset(h.p + hsize, 0, o - hsize); hsize = o + bytes; return o; }
     size_t take_scratch(size_t bytes) { const size_t o = (ssize + 255) & ~size_t(255); ssize = o + bytes; return o; }
     void reset() { hsize = 0; ssize = 0; }
 };
@@ -80,8 +79,8 @@ struct vil_ctx {
     hipStream_t stream = nullptr;
     Comm comm;                     // multi-GPU: rank, world, the transport and the owner table of the per-iteration message (vil_comm.hpp)
     Arena ar;
-    hipEvent_t dep_ev = nullptr;                           // orders the solve after a producer stream (vil_solve_device_lidar)
-    hipEvent_t up_ev = nullptr; bool up_pending = false;   // the DMA out of the pinned image must finish before the image is rewritten
+    vilhost::Fence dep_ev;                                 // orders the solve after a producer stream (vil_solve_device_lidar: its handle, in a hipStreamWaitEvent)
+    vilhost::Fence up_sent;                                // the DMA out of the pinned image must finish before the image is rewritten
     DevP P;                        // device pointers
     bool uploaded = false;
     int resident_kind = 0;         // 1: a window handed over through vil_upload / vil_solve (the only kind vil_solve_resident accepts);
@@ -102,26 +101,24 @@ struct vil_ctx {
     std::map<const void*, std::pair<size_t, int>> coop_caps;      // per kernel: (dynamic-LDS size probed last, workgroups the device holds at once AT that size) -- coop_capacity
     int vis_gm = 0;                      // doubles of operand rows the largest visual chunk of the uploaded window needs (vil_sweep.hpp)
     size_t span = 0;               // doubles of one linear-system set (SysBuf::ar): the multi-GPU all-reduce message
-    int* d_status = nullptr;
-    Ctl* h_ctl = nullptr;          // pinned
-    int* h_word = nullptr;         // pinned: status words read back from the device
-    char* h_mirror = nullptr; Ctl* d_hctl = nullptr; int* d_hseq = nullptr; double* d_hstate = nullptr; size_t mirror_ns = 0;      // pinned + mapped: Ctl | sequence word | final state, written by solve_finish (vil_finish.hpp)
+    vilhost::Grown<int> d_status;
+    vilhost::Grown<Ctl, true> h_ctl;          // pinned
+    vilhost::Grown<int, true> h_word;         // pinned: status words read back from the device (16 of them)
+    vilhost::Mapped h_mirror; Ctl* d_hctl = nullptr; int* d_hseq = nullptr; double* d_hstate = nullptr; size_t mirror_ns = 0;      // pinned + mapped: Ctl | sequence word | final state, written by solve_finish (vil_finish.hpp)
     bool no_poll = false;          // VIL_NO_POLL=1: copy + synchronise instead of polling the mirror
     bool mirror_state = false;     // the mirror holds the final state of the last solve (vil_download_state needs no device operation)
-    double* h_pin = nullptr;       // pinned scratch
-    char* marg_ws = nullptr;       // device work space of vil_marginalize (grow-only)
-    unsigned long long* d_marg_ts = nullptr;      // phase stamps of the last marginalisation's kernels (vil_debug_marg_stamps)
-    size_t marg_ws_bytes = 0;
-    size_t h_pin_bytes = 0;
+    vilhost::Grown<double, true> h_pin;       // pinned scratch
+    vilhost::Grown<char> marg_ws;             // device work space of vil_marginalize
+    unsigned long long* d_marg_ts = nullptr;      // phase stamps of the last marginalisation's kernels (vil_debug_marg_stamps): a place in marg_ws
     std::vector<int> prior_joff;
     bool sharded = false;          // the resident problem is this rank's shard of the factor set
     // hipGraph of a chunk of iterations, reused by repeated solves of one upload (key: chunk length, options)
     struct ChunkGraph { int n; SolveOpts so; hipGraphExec_t exec; };
     std::vector<ChunkGraph> graphs;
     int use_graph = -1;            // VIL_GRAPH=0 disables (tuning build)
-    int* d_imu_perm = nullptr;      // (vil_sweep.hpp, sweep_imu: entry order of the IMU roles)
+    vilhost::Grown<int> d_imu_perm;      // (vil_sweep.hpp, sweep_imu: entry order of the IMU roles)
     // (a few tables by key: a tracker alternates between the prior structures of its two marginalisation kinds, and a rebuild -- entries, sort, copy -- is ~80 us of host time)
-    struct ChTab { std::vector<int> key; int* d = nullptr; int* h = nullptr; size_t cap = 0; int n = 0; hipEvent_t ev = nullptr; bool ev_pending = false; unsigned long long used = 0; };
+    struct ChTab { std::vector<int> key; FrameStage st; int n = 0; unsigned long long used = 0; const int* d() const { return (const int*)st.d.p; } };      // (the table travels like a pushed frame)
     ChTab chtabs[4]; int chtab_cur = 0; unsigned long long chtab_clock = 0;      // gather table of the chain workgroup (vil_prechain.hpp)
     bool graph_failed = false;     // a chunk could not be captured / instantiated: direct launches from then on
     int fail_capture = 0;          // vil_debug_fail_graph_capture: that many captures are treated as failed
@@ -146,22 +143,29 @@ struct vil_ctx {
     bool profiling = false, stamps = false; long long period_n = 0;
     std::vector<unsigned long long> last_stamps;      // raw stamps of the last profiled solve (vil_debug_read_stamps)
     int wg_launch = -1;      // (vil_profile_workgroups)
-    long long* d_prof = nullptr; double phase_us[VIL_PROF_SLOTS] = {0}; long long phase_n = 0;      // phase stamps of the one-launch iterations (vil_profile_phases)
+    vilhost::Grown<long long> d_prof; double phase_us[VIL_PROF_SLOTS] = {0}; long long phase_n = 0;      // phase stamps of the one-launch iterations (vil_profile_phases)
     std::vector<hipEvent_t> ev, ev_mid, ev_coll;
     vil_profile prof = {0, 0.0, 0, 0.0, 0.0};
+    // what only the context can release (vil_destroy has selected the device and drained the stream); every member above then frees itself, with the
+    // device still current and the stream gone (vil_host.hpp)
+    ~vil_ctx() {
+        for (auto& e : ev) hipEventDestroy(e);
+        for (auto& e : ev_mid) hipEventDestroy(e);
+        for (auto& e : ev_coll) hipEventDestroy(e);
+        for (auto& g : graphs) hipGraphExecDestroy(g.exec);
+        comm.release(device);
+        if (stream) hipStreamDestroy(stream);
+    }
 };
 
 // pinned, device-mapped mirror [Ctl | sequence word (64 B) | final state (ns doubles)]; grow-only
 static int ensure_mirror(vil_ctx* c, size_t ns) {
-    if (c->h_mirror && ns <= c->mirror_ns) return VIL_OK;
+    if (c->h_mirror.h && ns <= c->mirror_ns) return VIL_OK;
     if (c->stream) HIPCHK(hipStreamSynchronize(c->stream));       // nobody is writing the old one
-    if (c->h_mirror) hipHostFree(c->h_mirror);
-    c->h_mirror = nullptr; c->d_hctl = nullptr; c->d_hseq = nullptr; c->d_hstate = nullptr; c->mirror_ns = 0; c->mirror_state = false;
+    c->d_hctl = nullptr; c->d_hseq = nullptr; c->d_hstate = nullptr; c->mirror_ns = 0; c->mirror_state = false;
     const size_t cap = ns + ns / 2 + 256, bytes = sizeof(Ctl) + 64 + 8 * cap;
-    HIPCHK(hipHostMalloc((void**)&c->h_mirror, bytes, hipHostMallocMapped));
-    memset(c->h_mirror, 0, bytes);
-    void* dp = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&dp, c->h_mirror, 0));
+    HIPCHK(c->h_mirror.open(bytes));                              // (releases the old one first)
+    void* const dp = c->h_mirror.d;
     c->d_hctl = (Ctl*)dp; c->d_hseq = (int*)((char*)dp + sizeof(Ctl)); c->d_hstate = (double*)((char*)dp + sizeof(Ctl) + 64);
     c->mirror_ns = cap;
     return VIL_OK;
@@ -288,6 +292,14 @@ void vil_default_options(vil_options* o) {
     o->autodiff_quirk = 1; o->precision = 0;
 }
 
+static int ctx_open(vil_ctx* c) {
+    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(c->d_status.reserve(1, 1));
+    HIPCHK(hipMemset(c->d_status.p, 0, sizeof(int)));
+    HIPCHK(c->h_ctl.reserve(1, 1));
+    HIPCHK(c->h_word.reserve(16, 16));      // small status reads land in PINNED memory (an asynchronous copy into pageable memory goes through the runtime's staging path)
+    return VIL_OK;
+}
 int vil_create(const vil_device_cfg* cfg, vil_ctx** out) {
     if (!cfg || !out) return VIL_ERR_INVALID_ARGUMENT;
     int ndev = 0;
@@ -296,42 +308,17 @@ int vil_create(const vil_device_cfg* cfg, vil_ctx** out) {
     HIPCHK(hipSetDevice(cfg->device));
     vil_ctx* c = new vil_ctx();
     c->device = cfg->device; c->comm.rank = cfg->rank; c->comm.world = cfg->world > 0 ? cfg->world : 1;
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc(&c->d_status, sizeof(int)));
-    HIPCHK(hipMemset(c->d_status, 0, sizeof(int)));
-    HIPCHK(hipHostMalloc(&c->h_ctl, sizeof(Ctl), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&c->h_word, 64, hipHostMallocDefault));      // small status reads land in PINNED memory (an asynchronous copy into pageable memory goes through the runtime's staging path)
     c->no_poll = getenv("VIL_NO_POLL") != nullptr;
     memset(&c->P, 0, sizeof c->P);
-    *out = c;
-    return VIL_OK;
+    const int st = ctx_open(c);
+    if (st != VIL_OK) vil_destroy(c); else *out = c;      // (a context that could not be opened goes the way every context goes)
+    return st;
 }
 
 void vil_destroy(vil_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev) hipEventDestroy(e);
-    for (auto& e : c->ev_mid) hipEventDestroy(e);
-    for (auto& e : c->ev_coll) hipEventDestroy(e);
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
-    c->comm.release(c->device);
-    if (c->ar.d) hipFree(c->ar.d);
-    if (c->ar.h) hipHostFree(c->ar.h);
-    if (c->up_ev) hipEventDestroy(c->up_ev);
-    if (c->dep_ev) hipEventDestroy(c->dep_ev);
-    if (c->d_status) hipFree(c->d_status);
-    if (c->h_ctl) hipHostFree(c->h_ctl);
-    if (c->h_word) hipHostFree(c->h_word);
-    if (c->h_mirror) hipHostFree(c->h_mirror);
-    if (c->h_pin) hipHostFree(c->h_pin);
-    if (c->marg_ws) hipFree(c->marg_ws);
-    if (c->d_imu_perm) hipFree(c->d_imu_perm);
-    for (auto& ct : c->chtabs) { if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h); if (ct.ev) hipEventDestroy(ct.ev); }
-    if (c->d_prof) hipFree(c->d_prof);
-    c->lidar.release();
-    c->win.release();
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -561,7 +548,7 @@ struct ImageBuilder {
         const size_t o = ar.take(bytes ? bytes : 8);
         if (o == (size_t)-1) { oom = true; return nullptr; }
         fix.push_back({o, slot, false});
-        return ar.h + o;
+        return ar.h.p + o;
     }
 };
 // the parameter block's header, constancy, state x[0], x[1] and its backups
@@ -709,14 +696,14 @@ static int upload_imu_prior(vil_ctx* c, ImageBuilder& im, const vil_problem* p, 
     im.put(nullptr, 8 * (size_t)225 * std::max(p->n_imu, 1), (void**)&P.imu_U);
     im.put(p->imu_i, 4 * (size_t)p->n_imu, (void**)&P.imu_i); im.put(p->imu_j, 4 * (size_t)p->n_imu, (void**)&P.imu_j);
     im.put(nullptr, 8 * (size_t)931 * std::max(p->n_imu, 1), (void**)&P.ipart);
-    if (!c->d_imu_perm) {   // the order of an IMU role's record entries in a one-launch iteration: what the chain workgroup gathers first.  Constant: one device copy per context
+    if (!c->d_imu_perm.p) {   // the order of an IMU role's record entries in a one-launch iteration: what the chain workgroup gathers first.  Constant: one device copy per context
         int perm[1024]; int n = VIL_CHAIN_REC;
         for (int e = 0; e < 931; ++e) { const int ce = chain_rec_index(e); if (ce >= 0) perm[ce] = e; else perm[n++] = e; }
         for (int e = 931; e < 1024; ++e) perm[e] = 930;
-        HIPCHK(hipMalloc((void**)&c->d_imu_perm, sizeof(perm)));
-        HIPCHK(hipMemcpy(c->d_imu_perm, perm, sizeof(perm), hipMemcpyHostToDevice));
+        HIPCHK(c->d_imu_perm.reserve(1024, 1024));
+        HIPCHK(hipMemcpy(c->d_imu_perm.p, perm, sizeof(perm), hipMemcpyHostToDevice));
     }
-    P.imu_perm = c->d_imu_perm;
+    P.imu_perm = c->d_imu_perm.p;
     im.put(nullptr, 4 * (size_t)(std::max(p->n_imu, 1) + 8), (void**)&P.cflag);
     im.put(nullptr, 8 * (size_t)VIL_CHAIN_REC * std::max(p->n_imu, 1), (void**)&P.irec);      // (compact IMU records for the chain workgroup of a one-launch iteration)
     P.pn = p->prior.n > 0 ? p->prior.n : 0; P.pnblk = P.pn ? p->prior.nblk : 0;
@@ -810,7 +797,7 @@ static int chain_table(vil_ctx* c, const vil_problem* p, bool sharded, DevP& P, 
     std::vector<int> key; key.reserve(2 * K + D + 2);
     key.push_back(K); key.push_back(P.pn); key.insert(key.end(), as_i.begin(), as_i.end()); key.insert(key.end(), as_j.begin(), as_j.end()); key.insert(key.end(), pinv.begin(), pinv.end());
     int cs = -1;
-    for (int q = 0; q < 4; ++q) if (c->chtabs[q].d && c->chtabs[q].key == key) cs = q;
+    for (int q = 0; q < 4; ++q) if (c->chtabs[q].d() && c->chtabs[q].key == key) cs = q;
     const bool ct_hit = cs >= 0;
     if (!ct_hit) { cs = 0; for (int q = 1; q < 4; ++q) if (c->chtabs[q].used < c->chtabs[cs].used) cs = q; }      // (least recently used)
     vil_ctx::ChTab& ct = c->chtabs[cs];
@@ -858,18 +845,10 @@ static int chain_table(vil_ctx* c, const vil_problem* p, bool sharded, DevP& P, 
         tab.insert(tab.end(), pq.begin(), pq.end());       // behind the table: the chain column -> prior column map
         while (tab.size() & 3) tab.push_back(0);
         const size_t bytes = 4 * tab.size();
-        if (ct.ev_pending) { HIPCHK(hipEventSynchronize(ct.ev)); ct.ev_pending = false; }      // the previous table's DMA has left the pinned copy
-        if (bytes > ct.cap) {
-            HIPCHK(hipStreamSynchronize(c->stream));      // (nobody reads the old one)
-            if (ct.d) hipFree(ct.d); if (ct.h) hipHostFree(ct.h);
-            ct.d = nullptr; ct.h = nullptr; ct.cap = 0;
-            HIPCHK(hipMalloc((void**)&ct.d, 2 * bytes)); HIPCHK(hipHostMalloc((void**)&ct.h, 2 * bytes, hipHostMallocDefault));
-            ct.cap = 2 * bytes;
-        }
-        memcpy(ct.h, tab.data(), bytes);
-        HIPCHK(hipMemcpyAsync(ct.d, ct.h, bytes, hipMemcpyHostToDevice, c->stream));
-        if (!ct.ev) HIPCHK(hipEventCreateWithFlags(&ct.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ct.ev, c->stream)); ct.ev_pending = true;
+        // the previous table's DMA has left the pinned copy; a larger pair once the stream is idle (nobody reads the old one)
+        { const int st = ct.st.begin(c->stream, bytes, 2 * bytes); if (st != VIL_OK) return st; }
+        memcpy(ct.st.h.p, tab.data(), bytes);
+        { const int st = ct.st.send(c->stream, bytes); if (st != VIL_OK) return st; }
         ct.n = ((int)tab.size() - ((9 * K + 3) & ~3)) / 4; ct.key.swap(key);
         built = true;
     }
@@ -882,11 +861,11 @@ static int commit(vil_ctx* c, ImageBuilder& im, DevP& P, bool pre_ok, const vil_
     Arena& ar = c->ar;
     if (im.oom) return VIL_ERR_DEVICE;
     const size_t tables = (ar.hsize + 255) & ~size_t(255), total = tables + ((ar.ssize + 255) & ~size_t(255));
-    if (total > ar.cap) { if (ar.d) HIPCHK(hipFree(ar.d)); ar.d = nullptr; ar.cap = 0; HIPCHK(hipMalloc(&ar.d, total + total / 4)); ar.cap = total + total / 4; }
-    for (const ImageBuilder::Fix& f : im.fix) *f.slot = ar.d + (f.scratch ? tables : 0) + f.off;
+    HIPCHK(ar.d.reserve(total, total + total / 4));
+    for (const ImageBuilder::Fix& f : im.fix) *f.slot = ar.d.p + (f.scratch ? tables : 0) + f.off;
     if (dl) { P.pl_c = dl->plane_soa; P.pl_stride = dl->plane_stride; P.ed_c = dl->edge_soa; P.ed_stride = dl->edge_stride; }
     if (!gp) { P.glm_start = P.lm_start; P.glm_acol = P.lm_acol; P.gfcol = P.fcol; }
-    if (pre_ok) { const vil_ctx::ChTab& ct = c->chtabs[c->chtab_cur]; P.chtab = ct.d; P.chpq = ct.d + 4 * (size_t)ct.n; }
+    if (pre_ok) { const vil_ctx::ChTab& ct = c->chtabs[c->chtab_cur]; P.chtab = ct.d(); P.chpq = ct.d() + 4 * (size_t)ct.n; }
     if (c->lidar_resident) c->lidar.tables(P);
     if (ws && P.pn) { P.px0 = ws->px0; P.pJ0 = ws->pJ0; P.pr0 = ws->pr0; P.pH = ws->pH; P.pg0 = ws->pg0; P.pc0 = ws->pc0; }      // the device prior slot, contractions included
     const size_t Lp = (size_t)std::max(P.L, 1), D = P.D;
@@ -896,17 +875,16 @@ static int commit(vil_ctx* c, ImageBuilder& im, DevP& P, bool pre_ok, const vil_
         sb.hll = sb.ar + ar_cam; sb.bl = sb.hll + Lp; sb.invp = sb.bl + Lp; sb.sl = sb.invp + Lp; sb.eA = sb.sl + Lp; sb.eO = sb.eA + 13 * Lp;
     }
     if (ar.hsize) {
-        HIPCHK(hipMemcpyAsync(ar.d, ar.h, ar.hsize, hipMemcpyHostToDevice, c->stream));
-        if (!c->up_ev) HIPCHK(hipEventCreateWithFlags(&c->up_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->up_ev, c->stream)); c->up_pending = true;
+        HIPCHK(hipMemcpyAsync(ar.d.p, ar.h.p, ar.hsize, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c->up_sent.record(c->stream));
     }
-    if (ar.ssize) HIPCHK(hipMemsetAsync(ar.d + tables, 0, ar.ssize, c->stream));
+    if (ar.ssize) HIPCHK(hipMemsetAsync(ar.d.p + tables, 0, ar.ssize, c->stream));
     P.drop_role = -1; P.drop_launch = -1;
     c->P = P; c->K = P.K; c->L = P.L; c->D = P.D; c->NS = P.NS;
     c->mirror_state = false;
     if (!c->no_poll) { const int ms = ensure_mirror(c, (size_t)P.NS); if (ms != VIL_OK) return ms; }
     c->P.hctl = c->d_hctl; c->P.hseq = c->d_hseq; c->P.hstate = c->d_hstate;
-    c->P.xorig = c->d_x0; c->P.gauge_on = c->gauge_on ? 1 : 0; c->P.setup_stat = c->d_status;
+    c->P.xorig = c->d_x0; c->P.gauge_on = c->gauge_on ? 1 : 0; c->P.setup_stat = c->d_status.p;
     return VIL_OK;
 }
 // what vil_marginalize_resident will need (a few passes over int tables; LiDAR points of pose 0 of a resident window: upload_lidar, from the unsliced slab counts)
@@ -1047,7 +1025,7 @@ static int choose_structure(vil_ctx* c, const vil_problem* p, bool pre_ok) {
 // one-time set-up: IMU sqrt-information, prior contraction
 static int upload_setup(vil_ctx* c, const WinSrc* ws, bool check_setup, const int* wd_track, const int* wd_startf) {
     const DevP& P = c->P;
-    if (!ws) HIPCHK(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));      // (resident window: nothing writes it -- its status word is the window's own, vil_win_solve -- and a 4-byte fill is a 5 us launch)
+    if (!ws) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int), c->stream));      // (resident window: nothing writes it -- its status word is the window's own, vil_win_solve -- and a 4-byte fill is a 5 us launch)
     if (ws) {
         // resident window: expand the landmark table into the factor tables, gather the IMU records, copy the state -- everything k_setup
         // would compute (sqrt-information, prior contractions) already sits next to its source
@@ -1062,13 +1040,13 @@ static int upload_setup(vil_ctx* c, const WinSrc* ws, bool check_setup, const in
         hipLaunchKernelGGL(k_win_pack, dim3(nbf + P.n_imu + nbs), dim3(256), 0, c->stream, W, nbf);
     }
     const int nb_setup = ws ? 0 : P.n_imu + (P.pn ? 64 : 0);
-    if (nb_setup > 0) hipLaunchKernelGGL(k_setup, dim3(nb_setup), dim3(VIL_THREADS), 0, c->stream, P, const_cast<double*>(P.imu_U), c->d_status);
+    if (nb_setup > 0) hipLaunchKernelGGL(k_setup, dim3(nb_setup), dim3(VIL_THREADS), 0, c->stream, P, const_cast<double*>(P.imu_U), c->d_status.p);
     if (check_setup) {
-        c->h_word[0] = 0;
-        HIPCHK(hipMemcpyAsync(c->h_word, c->d_status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        c->h_word.p[0] = 0;
+        HIPCHK(hipMemcpyAsync(c->h_word.p, c->d_status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipGetLastError());
-        if (c->h_word[0] != 0) return VIL_ERR_NOT_POSITIVE_DEFINITE;
+        if (c->h_word.p[0] != 0) return VIL_ERR_NOT_POSITIVE_DEFINITE;
     }
     return VIL_OK;
 }
@@ -1089,7 +1067,7 @@ static int upload_impl(vil_ctx* c, const vil_problem* p, const vil_state* s, boo
 #else
     #define UPTICK(name) do {} while (0)
 #endif
-    if (c->up_pending) { HIPCHK(hipEventSynchronize(c->up_ev)); c->up_pending = false; }
+    HIPCHK(c->up_sent.wait());
     c->ar.reset();
     ImageBuilder im{c->ar};
     DevP P; memset(&P, 0, sizeof P);
@@ -1180,14 +1158,14 @@ static int launch_sweep(vil_ctx* c, const SolveOpts& so) {
 static int launch_iter(vil_ctx* c, const SolveOpts& so) {
     DevP Pi = c->P;
     Pi.gather_pose_only = 1;
-    Pi.prof = c->profiling ? c->d_prof : nullptr; Pi.wg_launch = c->profiling ? c->wg_launch : -1;
+    Pi.prof = c->profiling ? c->d_prof.p : nullptr; Pi.wg_launch = c->profiling ? c->wg_launch : -1;
     launch_chosen(c, c->ls.iter_fn, c->ls.n_sweep + 1 + c->ls.n_gather_m + 1 + c->P.n_help + c->ls.n_ww, VIL_STEP_THREADS, c->ls.lds_iter, Pi, so);      // [sweep roles | chain | master | helpers | W W^T tiles | gather]
     return VIL_OK;
 }
 // the whole solve as ONE resident launch (vil_iter.hpp, k_solve); budget_ticks: what is left of max_time_s on the device's 100 MHz clock (0: no cap)
 static int launch_solve(vil_ctx* c, const SolveOpts& so, long long budget_ticks) {
     DevP Pi = c->P;
-    Pi.gather_pose_only = 1; Pi.prof = c->stamps ? c->d_prof : nullptr; Pi.wg_launch = -1; Pi.persist = 1;
+    Pi.gather_pose_only = 1; Pi.prof = c->stamps ? c->d_prof.p : nullptr; Pi.wg_launch = -1; Pi.persist = 1;
     vil_k_solve_launch(c->P.vis_ts, (unsigned)(c->ls.n_sweep + 2 + c->P.n_help + c->ls.n_ww), c->ls.lds_solve, c->stream, Pi, so, budget_ticks);      // [sweep roles | chain | master | helpers | W W^T tiles]
     return VIL_OK;
 }
@@ -1236,7 +1214,7 @@ static int init_ctl(vil_ctx* c, const vil_options* o, int lin_mode) {
         double* const xs = lin_mode == 0 ? c->d_xsave : nullptr;      // (a solve keeps its start state aside: vil_solve_resident's retry / failure path)
         hipLaunchKernelGGL(k_solve_init, dim3(xs ? (c->NS + 255) / 256 : 1), dim3(256), 0, c->stream, c->P.ctl, ++c->solve_gen, o->initial_radius, o->min_mu, lin_mode, c->P.abortf, (const double*)c->P.x[0], xs, c->NS);
     }
-    memset(c->h_ctl, 0, sizeof(Ctl));
+    memset(c->h_ctl.p, 0, sizeof(Ctl));
     return VIL_OK;
 }
 
@@ -1244,7 +1222,7 @@ int vil_profile_enable(vil_ctx* c, int on) {
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
     if (on && c->ev.empty()) { c->ev.resize(2 * VIL_MAX_CHUNK + 2); for (auto& e : c->ev) HIPCHK(hipEventCreate(&e)); c->ev_mid.resize(VIL_MAX_CHUNK + 1); for (auto& e : c->ev_mid) HIPCHK(hipEventCreate(&e)); c->ev_coll.resize(VIL_MAX_CHUNK + 1); for (auto& e : c->ev_coll) HIPCHK(hipEventCreate(&e)); }
-    if (on && !c->d_prof) { HIPCHK(hipMalloc((void**)&c->d_prof, 8 * (64 * VIL_PROF_SLOTS + 2 * VIL_PROF_WGS))); HIPCHK(hipMemset(c->d_prof, 0, 8 * (64 * VIL_PROF_SLOTS + 2 * VIL_PROF_WGS))); }
+    if (on && !c->d_prof.p) { HIPCHK(c->d_prof.reserve(64 * VIL_PROF_SLOTS + 2 * VIL_PROF_WGS, 64 * VIL_PROF_SLOTS + 2 * VIL_PROF_WGS)); HIPCHK(hipMemset(c->d_prof.p, 0, 8 * (64 * VIL_PROF_SLOTS + 2 * VIL_PROF_WGS))); }
     c->profiling = on == 1;
     c->stamps = on == 2;          // 2: the phase stamps alone -- the launch structure stays the library's choice (the persistent solve keeps its one launch; no events)
     return VIL_OK;
@@ -1365,11 +1343,11 @@ static int enqueue_chunk(vil_ctx* c, const Attempt& a, int n) {
 // solve_finish leaves Ctl, the final state and then the solve generation in pinned host memory: poll that word instead of
 // synchronising (the no-op tail of the chunk is not waited for, nothing is copied afterwards).  A chunk that runs out without
 // finishing is seen by hipStreamQuery and takes the copy + synchronise route, as do profiling and multi-rank solves.
-// Leaves *c->h_ctl filled; *via_mirror is set when it came through the mirror.
+// Leaves *c->h_ctl.p filled; *via_mirror is set when it came through the mirror.
 static int await_result(vil_ctx* c, bool* via_mirror) {
     bool polled = false;
     if (c->d_hseq && !c->profiling && !(c->split && c->comm.host_synchronised())) {
-        volatile int* seq = (volatile int*)(c->h_mirror + sizeof(Ctl));
+        volatile int* seq = (volatile int*)(c->h_mirror.h + sizeof(Ctl));
         const int gen = c->solve_gen;
         const auto tp0 = std::chrono::steady_clock::now();
         for (long spin = 1;; ++spin) {
@@ -1381,17 +1359,17 @@ static int await_result(vil_ctx* c, bool* via_mirror) {
                 if (std::chrono::steady_clock::now() - tp0 > std::chrono::seconds(2)) break;
             }
         }
-        if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_ctl, c->h_mirror, sizeof(Ctl)); *via_mirror = true; }
+        if (polled) { std::atomic_thread_fence(std::memory_order_acquire); memcpy(c->h_ctl.p, c->h_mirror.h, sizeof(Ctl)); *via_mirror = true; }
     }
     if (!polled) {
-        HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_ctl.p, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return VIL_OK;
 }
 // profiling: the HIP events of a chunk of `launched` direct launches, for those of them that found the solve unfinished
 static int account_events(vil_ctx* c, bool fused, int launched, int sweeps_before) {
-    int live = c->h_ctl->n_sweeps - sweeps_before;   // launches that found done == 0
+    int live = c->h_ctl.p->n_sweeps - sweeps_before;   // launches that found done == 0
     live = std::max(0, std::min(live, launched));
     for (int q = 0; q < live; ++q) {
         float ms = 0.f;
@@ -1414,14 +1392,14 @@ static bool host_cap_reached(const vil_ctx* c, const Attempt& a) {
 // ceres max_solver_time_in_seconds (estimator.cpp:1411): the host ends the solve; the accepted state is written out on request
 static int finish_at_cap(vil_ctx* c) {
     hipLaunchKernelGGL(k_finish, dim3(1), dim3(VIL_SWEEP_THREADS), 0, c->stream, c->P, (int)VIL_TERM_MAX_TIME);
-    HIPCHK(hipMemcpyAsync(c->h_ctl, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_ctl.p, c->P.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return VIL_OK;
 }
 // the launches' own clock stamps (100 MHz): the sweep phase of a one-launch iteration = first workgroup started -> last sweep role posted
 static int account_stamps(vil_ctx* c, bool persist, int n_sweeps) {
     std::vector<unsigned long long>& hp = c->last_stamps; hp.assign((size_t)64 * VIL_PROF_SLOTS, 0ull);
-    HIPCHK(hipMemcpyAsync(hp.data(), c->d_prof, 8 * hp.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hp.data(), c->d_prof.p, 8 * hp.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (persist && c->stamps && !c->ev.empty()) {      // the resident launch as a whole (HIP events on the library's stream): step_ms / step_launches; its iterations: sweep_launches
         float ms = 0.f;
@@ -1447,7 +1425,7 @@ static int account_stamps(vil_ctx* c, bool persist, int n_sweeps) {
 }
 // Ctl -> vil_summary, the history that sizes the next solve's first chunk, and the status of the attempt
 static int summarize(vil_ctx* c, const Attempt& a, bool via_mirror, vil_summary* sum) {
-    const Ctl& ctl = *c->h_ctl;
+    const Ctl& ctl = *c->h_ctl.p;
     c->solves_since_upload++;
     c->last_live = ctl.n_sweeps;
     c->recent_live[c->recent_at++ & 7] = ctl.n_sweeps;
@@ -1471,14 +1449,14 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
     *gave_up = false;
     int st = init_ctl(c, o, 0);
     if (st != VIL_OK) return st;
-    const bool stamped = (c->profiling || (c->stamps && a.persist())) && a.fused() && c->d_prof != nullptr;      // the launches leave their own clock stamps in d_prof
-    if (stamped) HIPCHK(hipMemsetAsync(c->d_prof, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
+    const bool stamped = (c->profiling || (c->stamps && a.persist())) && a.fused() && c->d_prof.p != nullptr;      // the launches leave their own clock stamps in d_prof
+    if (stamped) HIPCHK(hipMemsetAsync(c->d_prof.p, 0, 8 * 64 * VIL_PROF_SLOTS, c->stream));
     // every iteration = sweep + gather + step kernel; `done` turns the tail of a chunk into no-ops, and the first sweep launch that finds
     // the solve finished writes the result out (vil_finish.hpp); k_finish at the end of every chunk covers a solve that ends in its last iteration
     bool finished = false, via_mirror = false;
     int chunk = first_chunk(c, a.fused());
     for (int it = 0; it <= o->max_iterations + 8 && !finished; chunk = 3) {
-        const int sweeps_before = (it == 0) ? 0 : c->h_ctl->n_sweeps;
+        const int sweeps_before = (it == 0) ? 0 : c->h_ctl.p->n_sweeps;
         const int left = o->max_iterations + 9 - it, nthis = std::min(chunk, left);
         hipGraphExec_t exec = nullptr;
         if (may_replay(c, a)) { st = chunk_graph(c, a, nthis, &exec); if (st != VIL_OK) return st; }
@@ -1490,14 +1468,14 @@ static int solve_attempt(vil_ctx* c, const vil_options* o, vil_summary* sum, con
         it += n;
         st = await_result(c, &via_mirror);
         if (st != VIL_OK) return st;
-        finished = c->h_ctl->done != 0;
+        finished = c->h_ctl.p->done != 0;
         if (c->profiling) { st = account_events(c, a.fused(), n, sweeps_before); if (st != VIL_OK) return st; }
         if (!finished && host_cap_reached(c, a)) { st = finish_at_cap(c); if (st != VIL_OK) return st; finished = true; via_mirror = false; }
     }
     HIPCHK(hipGetLastError());
     // a wait inside a launch gave up (vil_math.hpp, spin_until_eq): the master ended the solve with status -2 -- or never ran, and the launches drained without a `done`
-    if (!finished || c->h_ctl->status == VIL_ERR_DEVICE) { *gave_up = true; return VIL_ERR_DEVICE; }
-    if (stamped && c->h_ctl->n_sweeps <= 64) { st = account_stamps(c, a.persist(), c->h_ctl->n_sweeps); if (st != VIL_OK) return st; }
+    if (!finished || c->h_ctl.p->status == VIL_ERR_DEVICE) { *gave_up = true; return VIL_ERR_DEVICE; }
+    if (stamped && c->h_ctl.p->n_sweeps <= 64) { st = account_stamps(c, a.persist(), c->h_ctl.p->n_sweeps); if (st != VIL_OK) return st; }
     return summarize(c, a, via_mirror, sum);
 }
 
@@ -1611,7 +1589,7 @@ int vil_download_state(vil_ctx* c, vil_state* s) {
     flush_reset(c);
     const double* x = nullptr;
     std::vector<double> xb;
-    if (c->mirror_state) x = (const double*)(c->h_mirror + sizeof(Ctl) + 64);      // left there by solve_finish: no device operation
+    if (c->mirror_state) x = (const double*)(c->h_mirror.h + sizeof(Ctl) + 64);      // left there by solve_finish: no device operation
     else {
         xb.resize(c->NS);
         HIPCHK(hipMemcpyAsync(xb.data(), c->P.x[0], 8 * (size_t)c->NS, hipMemcpyDeviceToHost, c->stream));
@@ -1648,9 +1626,8 @@ int vil_solve_device_lidar(vil_ctx* c, const vil_problem* p, const vil_device_li
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(c->device));
     if (producer_stream && (hipStream_t)producer_stream != c->stream) {      // the tables are written by work on another stream: order after it on the device
-        if (!c->dep_ev) HIPCHK(hipEventCreateWithFlags(&c->dep_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->dep_ev, (hipStream_t)producer_stream));
-        HIPCHK(hipStreamWaitEvent(c->stream, c->dep_ev, 0));
+        HIPCHK(c->dep_ev.record((hipStream_t)producer_stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->dep_ev.ev, 0));
     }
     int st = upload_impl(c, p, s, false, dl);
     if (st != VIL_OK) return st;
@@ -1665,14 +1642,7 @@ int vil_solve_device_lidar(vil_ctx* c, const vil_problem* p, const vil_device_li
     return st;
 }
 
-static int ensure_pin(vil_ctx* c, size_t bytes) {
-    if (bytes <= c->h_pin_bytes) return VIL_OK;
-    if (c->h_pin) hipHostFree(c->h_pin);
-    c->h_pin = nullptr; c->h_pin_bytes = 0;
-    HIPCHK(hipHostMalloc(&c->h_pin, bytes, hipHostMallocDefault));
-    c->h_pin_bytes = bytes;
-    return VIL_OK;
-}
+static hipError_t ensure_pin(vil_ctx* c, size_t bytes) { return c->h_pin.reserve((bytes + 7) / 8, (bytes + 7) / 8); }
 
 int vil_eval_factors(vil_ctx* c, const vil_problem* p, const vil_state* s, int cls, double* r, double* J) {
     if (!c || !r) return VIL_ERR_INVALID_ARGUMENT;
@@ -1692,10 +1662,10 @@ int vil_eval_factors(vil_ctx* c, const vil_problem* p, const vil_state* s, int c
     }
     if (nfac == 0) return VIL_OK;
     const size_t br = 8 * nr * nfac, bj = J ? 8 * nj * nfac : 0;
-    double *d_r = nullptr, *d_J = nullptr; int* d_joff = nullptr;
-    struct Free { double*& r; double*& J; int*& o; ~Free() { if (r) hipFree(r); if (J) hipFree(J); if (o) hipFree(o); } } free_tmp{d_r, d_J, d_joff};   // also on the error returns
-    HIPCHK(hipMalloc(&d_r, br));
-    if (J) HIPCHK(hipMalloc(&d_J, bj));
+    vilhost::Grown<char> t_r, t_J; vilhost::Grown<int> t_joff;      // (freed on every return)
+    HIPCHK(t_r.reserve(br, br));
+    if (J) HIPCHK(t_J.reserve(bj, bj));
+    double* const d_r = (double*)t_r.p; double* const d_J = (double*)t_J.p;
     const double* x = P.x[0];
     const int nb = (nfac + VIL_THREADS - 1) / VIL_THREADS;
     switch (cls) {
@@ -1706,18 +1676,17 @@ int vil_eval_factors(vil_ctx* c, const vil_problem* p, const vil_state* s, int c
         case VIL_FACTOR_EDGE: hipLaunchKernelGGL(k_eval_lidar<3>, dim3(nb), dim3(VIL_THREADS), 0, c->stream, P, x, d_r, d_J); break;
         case VIL_FACTOR_PLANE: hipLaunchKernelGGL(k_eval_lidar<1>, dim3(nb), dim3(VIL_THREADS), 0, c->stream, P, x, d_r, d_J); break;
         case VIL_FACTOR_PRIOR:
-            HIPCHK(hipMalloc(&d_joff, 4 * c->prior_joff.size()));
-            HIPCHK(hipMemcpyAsync(d_joff, c->prior_joff.data(), 4 * c->prior_joff.size(), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_eval_prior, dim3(1), dim3(VIL_THREADS), 8 * (size_t)P.pn, c->stream, P, x, d_r, d_J, d_joff);
+            HIPCHK(t_joff.reserve(c->prior_joff.size(), c->prior_joff.size()));
+            HIPCHK(hipMemcpyAsync(t_joff.p, c->prior_joff.data(), 4 * c->prior_joff.size(), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_eval_prior, dim3(1), dim3(VIL_THREADS), 8 * (size_t)P.pn, c->stream, P, x, d_r, d_J, t_joff.p);
             break;
     }
-    st = ensure_pin(c, br + bj);
-    if (st != VIL_OK) return st;
-    HIPCHK(hipMemcpyAsync(c->h_pin, d_r, br, hipMemcpyDeviceToHost, c->stream));
-    if (J) HIPCHK(hipMemcpyAsync((char*)c->h_pin + br, d_J, bj, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(ensure_pin(c, br + bj));
+    HIPCHK(hipMemcpyAsync(c->h_pin.p, d_r, br, hipMemcpyDeviceToHost, c->stream));
+    if (J) HIPCHK(hipMemcpyAsync((char*)c->h_pin.p + br, d_J, bj, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
-    const double* hr = c->h_pin; const double* hj = (const double*)((char*)c->h_pin + br);
+    const double* hr = c->h_pin.p; const double* hj = (const double*)((char*)c->h_pin.p + br);
     if (cls == VIL_FACTOR_EDGE || cls == VIL_FACTOR_PLANE) {   // undo the pose sort
         const std::vector<int>& perm = cls == VIL_FACTOR_EDGE ? c->edge_perm : c->plane_perm;
         for (int sidx = 0; sidx < nfac; ++sidx) {
@@ -1739,10 +1708,10 @@ int vil_eval_lidar_functors(vil_ctx* c, int32_t kind, int32_t n, const double* c
       for (int i = 0; i < 3; ++i) A.tbl[i] = -(A.Rbl[3 * i] * t_lb[0] + A.Rbl[3 * i + 1] * t_lb[1] + A.Rbl[3 * i + 2] * t_lb[2]); }
     memcpy(A.pose, pose7, sizeof A.pose);
     const size_t bc = 8 * (size_t)nc * n, br = 8 * (size_t)nr * n, bj = J ? 8 * (size_t)nr * 7 * n : 0;
-    double *d_c = nullptr, *d_r = nullptr, *d_J = nullptr;
-    struct Free { double*& a; double*& b; double*& c; ~Free() { if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); } } free_tmp{d_c, d_r, d_J};
-    HIPCHK(hipMalloc(&d_c, bc)); HIPCHK(hipMalloc(&d_r, br));
-    if (J) HIPCHK(hipMalloc(&d_J, bj));
+    vilhost::Grown<char> t_c, t_r, t_J;      // (freed on every return)
+    HIPCHK(t_c.reserve(bc, bc)); HIPCHK(t_r.reserve(br, br));
+    if (J) HIPCHK(t_J.reserve(bj, bj));
+    double* const d_c = (double*)t_c.p; double* const d_r = (double*)t_r.p; double* const d_J = (double*)t_J.p;
     HIPCHK(hipMemcpyAsync(d_c, consts, bc, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_eval_lidar_functors, dim3((n + VIL_THREADS - 1) / VIL_THREADS), dim3(VIL_THREADS), 0, c->stream, (int)kind, (int)n, d_c, A, d_r, d_J);
     HIPCHK(hipMemcpyAsync(r, d_r, br, hipMemcpyDeviceToHost, c->stream));
@@ -1762,15 +1731,14 @@ int vil_linearize(vil_ctx* c, const vil_problem* p, const vil_state* s, const vi
     launch_sweep(c, so);                                   // partial records of system set 1 (cand = 1 - cur)
     launch_reduce_step(c, so, false);
     const size_t D = c->D;
-    st = ensure_pin(c, 8 * (D * D + D + 1));
-    if (st != VIL_OK) return st;
+    HIPCHK(ensure_pin(c, 8 * (D * D + D + 1)));
     const double* src = c->P.sys[1].ar;        // un-sharded: the candidate set (cur = 0); sharded: the all-reduced set
-    HIPCHK(hipMemcpyAsync(c->h_pin, src, 8 * D * D, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_pin + D * D, src + D * D, 8 * D, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_pin + D * D + D, src + D * D + 3 * D, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pin.p, src, 8 * D * D, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pin.p + D * D, src + D * D, 8 * D, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pin.p + D * D + D, src + D * D + 3 * D, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
-    memcpy(S, c->h_pin, 8 * D * D); memcpy(g, c->h_pin + D * D, 8 * D); *cost = c->h_pin[D * D + D];
+    memcpy(S, c->h_pin.p, 8 * D * D); memcpy(g, c->h_pin.p + D * D, 8 * D); *cost = c->h_pin.p[D * D + D];
     return VIL_OK;
 }
 
@@ -1797,13 +1765,8 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
     // ---- device work space + kernel ------------------------------------------------------------------------------
     const size_t nn = (size_t)n * n;
     const size_t bytes = 8 * ((size_t)nd * nd * 2 + nd + nn * 5 + (size_t)n * 3) + 4 * (size_t)(nd + n) + 8192 + 256;
-    if (bytes > c->marg_ws_bytes) {          // grow-only work space: no allocation on the per-frame path once warm
-        if (c->marg_ws) hipFree(c->marg_ws);
-        c->marg_ws = nullptr; c->marg_ws_bytes = 0;
-        HIPCHK(hipMalloc(&c->marg_ws, bytes));
-        c->marg_ws_bytes = bytes;
-    }
-    char* dw = c->marg_ws;
+    HIPCHK(c->marg_ws.reserve(bytes, bytes));      // grow-only work space: no allocation on the per-frame path once warm
+    char* dw = c->marg_ws.p;
     size_t off = 0;
     auto take = [&](size_t b2) { char* r = dw + off; off += (b2 + 255) & ~size_t(255); return r; };
     MargDev M;
@@ -1820,9 +1783,8 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
     if (off > bytes) return VIL_ERR_DEVICE;
     // the column table travels through pinned memory: the copy is asynchronous and the resident window never waits for it (the next use
     // of this staging area is a whole solve away)
-    st = ensure_pin(c, 8 * (nn * 2 + 2 * (size_t)n + 16 * (size_t)K + 8) + 4 * (size_t)(nd + n) + 64);
-    if (st != VIL_OK) return st;
-    int* hcols = (int*)((char*)c->h_pin + 8 * (nn * 2 + 2 * (size_t)n + 16 * (size_t)K + 8));
+    HIPCHK(ensure_pin(c, 8 * (nn * 2 + 2 * (size_t)n + 16 * (size_t)K + 8) + 4 * (size_t)(nd + n) + 64));
+    int* hcols = (int*)((char*)c->h_pin.p + 8 * (nn * 2 + 2 * (size_t)n + 16 * (size_t)K + 8));
     for (int q = 0; q < nd; ++q) hcols[q] = drop_cols[q];
     for (int q = 0; q < n; ++q) hcols[nd + q] = keep_cols[q];
     HIPCHK(hipMemcpyAsync(d_drop, hcols, 4 * (size_t)(nd + n), hipMemcpyHostToDevice, c->stream));
@@ -1854,22 +1816,22 @@ static int marg_finish(vil_ctx* c, const int K, const bool old_, const int drop_
         return VIL_OK;
     }
     const size_t ncam = 16 * (size_t)K + 8;
-    HIPCHK(hipMemcpyAsync(c->h_pin, M.J0, 8 * (2 * nn + 2 * (size_t)n), hipMemcpyDeviceToHost, c->stream));      // J0 | A | r0 | b
+    HIPCHK(hipMemcpyAsync(c->h_pin.p, M.J0, 8 * (2 * nn + 2 * (size_t)n), hipMemcpyDeviceToHost, c->stream));      // J0 | A | r0 | b
     // x0 of the new prior = the state the factors were LINEARISED at, i.e. the device state (the reference stores the very values it
     // marginalises at, marginalization_factor.cpp:110-139) -- not whatever the caller holds
-    double* hx = c->h_pin + 2 * nn + 2 * (size_t)n;
+    double* hx = c->h_pin.p + 2 * nn + 2 * (size_t)n;
     HIPCHK(hipMemcpyAsync(hx, c->P.x[0], 8 * ncam, hipMemcpyDeviceToHost, c->stream));
     int mstat[4] = {0, 0, 0, 0};
     if (VIL_TUNE_ENV("VIL_MARG_DEBUG")) HIPCHK(hipMemcpyAsync(mstat, M.stat, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
     if (VIL_TUNE_ENV("VIL_MARG_DEBUG")) fprintf(stderr, "[vil_marginalize] n=%d nd=%d one-sided Jacobi stages: %d (dropped block) %d (n x n, %.1f sweeps)\n", n, nd, mstat[0], mstat[1], mstat[1] / (double)(((n + 1) & ~1) - 1));
-    for (size_t e = 0; e < 2 * nn + 2 * (size_t)n; ++e) if (!std::isfinite(c->h_pin[e])) return VIL_ERR_NON_FINITE;
+    for (size_t e = 0; e < 2 * nn + 2 * (size_t)n; ++e) if (!std::isfinite(c->h_pin.p[e])) return VIL_ERR_NON_FINITE;
     // ---- getParameterBlocks with the address shift as an index remap (estimator.cpp:1599-1611, 1654-1677) --------------
     out->n = n; out->m = nd + n_lm_elim; out->nblk = (int)kinds.size();
-    memcpy(out->J0, c->h_pin, 8 * nn); memcpy(out->r0, c->h_pin + 2 * nn, 8 * (size_t)n);
-    if (out->A) memcpy(out->A, c->h_pin + nn, 8 * nn);
-    if (out->b) memcpy(out->b, c->h_pin + 2 * nn + n, 8 * (size_t)n);
+    memcpy(out->J0, c->h_pin.p, 8 * nn); memcpy(out->r0, c->h_pin.p + 2 * nn, 8 * (size_t)n);
+    if (out->A) memcpy(out->A, c->h_pin.p + nn, 8 * nn);
+    if (out->b) memcpy(out->b, c->h_pin.p + 2 * nn + n, 8 * (size_t)n);
     int col = 0, xo = 0;
     for (size_t b = 0; b < kinds.size(); ++b) {
         const int kind = kinds[b], idx = index[b];
@@ -2186,7 +2148,7 @@ int vil_win_marginalize(vil_ctx* c, const vil_options* o, const vil_marg_spec* s
 int vil_win_prior_download(vil_ctx* c, vil_prior_out* out) {
     if (!c || !out || !c->win.is_open) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(c->device));
-    return c->win.prior_download(c->stream, out, &c->h_word[8]);
+    return c->win.prior_download(c->stream, out, &c->h_word.p[8]);
 }
 
 int vil_win_prior_set(vil_ctx* c, const vil_prior* pr) {
@@ -2247,12 +2209,15 @@ static int debug_dense_run(vil_ctx* c, int32_t D, const double* A, const double*
     HIPCHK(hipSetDevice(c->device));
     const int R = D + 1, T = (R + 15) / 16, nt = T * (T + 1) / 2;
     const size_t lds = 8 * (size_t)TILE_SZ * nt, nb = 8 * (size_t)R * R;
-    double *dA = nullptr, *dL = nullptr, *dx = nullptr, *dW = nullptr, *dWW = nullptr, *dsc = nullptr; int* dok = nullptr;
-    HIPCHK(hipMalloc((void**)&dA, nb)); HIPCHK(hipMalloc((void**)&dL, nb)); HIPCHK(hipMalloc((void**)&dx, 8 * (size_t)R)); HIPCHK(hipMalloc((void**)&dok, 64));
+    const size_t nRR = (size_t)R * R;
+    vilhost::Grown<double> tA, tL, tx, tW, tWW, tsc; vilhost::Grown<int> tok;      // (freed on every return)
+    HIPCHK(tA.reserve(nRR, nRR)); HIPCHK(tL.reserve(nRR, nRR)); HIPCHK(tx.reserve(R, R)); HIPCHK(tok.reserve(16, 16));
+    double *dA = tA.p, *dL = tL.p, *dx = tx.p, *dW = nullptr, *dWW = nullptr, *dsc = nullptr; int* dok = tok.p;
     HIPCHK(hipMemcpy(dA, A, nb, hipMemcpyHostToDevice));
     const void* fn;
     if (WW) {
-        HIPCHK(hipMalloc((void**)&dW, nb)); HIPCHK(hipMalloc((void**)&dWW, 8 * (size_t)256 * nt)); HIPCHK(hipMalloc((void**)&dsc, 8 * (size_t)D));
+        HIPCHK(tW.reserve(nRR, nRR)); HIPCHK(tWW.reserve((size_t)256 * nt, (size_t)256 * nt)); HIPCHK(tsc.reserve(D, D));
+        dW = tW.p; dWW = tWW.p; dsc = tsc.p;
         HIPCHK(hipMemcpy(dW, WW, nb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dsc, sc, 8 * (size_t)D, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_debug_ww_fill, dim3(nt), dim3(256), 0, c->stream, dW, dWW, D, pad);
         const bool small = nt <= 24;                     // (the step's own choice: solve_prechain)
@@ -2268,7 +2233,6 @@ static int debug_dense_run(vil_ctx* c, int32_t D, const double* A, const double*
     int hok = 0;
     HIPCHK(hipMemcpy(L, dL, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(x, dx, 8 * (size_t)D, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hok, dok, 4, hipMemcpyDeviceToHost));
     *ok = hok;
-    hipFree(dA); hipFree(dL); hipFree(dx); hipFree(dok); hipFree(dW); hipFree(dWW); hipFree(dsc);
     return VIL_OK;
 }
 int vil_debug_dense_solve(vil_ctx* c, int32_t D, const double* A, double* L, double* x, int32_t* ok, int32_t variant) { return debug_dense_run(c, D, A, nullptr, nullptr, 0.0, L, x, ok, variant); }
@@ -2299,13 +2263,13 @@ int vil_profile_workgroups(vil_ctx* c, int32_t launch, uint64_t* times, int32_t 
     if (!c) return VIL_ERR_INVALID_ARGUMENT;
     if (!times) {                                         // arm: the solves from now on record launch `launch` (< 0: none)
         c->wg_launch = launch;
-        if (c->d_prof) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMemset((char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 0, 8 * 2 * VIL_PROF_WGS)); }
+        if (c->d_prof.p) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMemset((char*)c->d_prof.p + 8 * 64 * VIL_PROF_SLOTS, 0, 8 * 2 * VIL_PROF_WGS)); }
         return VIL_OK;
     }
-    if (!c->d_prof || max_workgroups < 0) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c->d_prof.p || max_workgroups < 0) return VIL_ERR_INVALID_ARGUMENT;
     HIPCHK(hipStreamSynchronize(c->stream));
     const int n = std::min<int>(max_workgroups, VIL_PROF_WGS);
-    HIPCHK(hipMemcpy(times, (char*)c->d_prof + 8 * 64 * VIL_PROF_SLOTS, 8 * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(times, (char*)c->d_prof.p + 8 * 64 * VIL_PROF_SLOTS, 8 * 2 * (size_t)n, hipMemcpyDeviceToHost));
     return VIL_OK;
 }
 int vil_debug_read_stamps(vil_ctx* c, uint64_t* out, int32_t max_launches) {

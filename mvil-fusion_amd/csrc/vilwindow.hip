@@ -1,5 +1,5 @@
 // vilwindow.hip -- the LiDAR frame slabs and the fully resident window of libvilsolve.so (vil_resident.hpp; device layout: vil_window.hpp): slot bookkeeping,
-// the per-frame staging DMA, allocation and teardown, and the kernels only this store launches.
+// the per-frame staging DMA, allocation (every buffer a vilhost::Grown: no teardown of its own), and the kernels only this store launches.
 #include <algorithm>
 #include <cstring>
 #include "vil_resident.hpp"
@@ -102,24 +102,17 @@ __global__ void k_aos2soa(const double* aos, int n, int ncomp, double* dst, size
 
 // ---- the staging pair -------------------------------------------------------------------------------------------------------------
 int FrameStage::begin(hipStream_t stream, size_t bytes, size_t grow_to) {
-    if (pending) { HIPCHK(hipEventSynchronize(ev)); pending = false; }
-    if (bytes <= cap) return VIL_OK;
+    HIPCHK(sent.wait());
+    if (bytes <= d.cap) return VIL_OK;                   // (the twin is allocated last: it is there only when both are)
     HIPCHK(hipStreamSynchronize(stream));                // (a kernel may still be reading the device twin)
-    if (h) hipHostFree(h); if (d) hipFree(d);
-    h = nullptr; d = nullptr; cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h, grow_to, hipHostMallocDefault)); HIPCHK(hipMalloc((void**)&d, grow_to));
-    cap = grow_to;
+    h.release(); d.release();
+    HIPCHK(h.reserve(grow_to, grow_to)); HIPCHK(d.reserve(grow_to, grow_to));
     return VIL_OK;
 }
 int FrameStage::send(hipStream_t stream, size_t bytes) {
-    HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream));
-    if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ev, stream)); pending = true;
+    HIPCHK(hipMemcpyAsync(d.p, h.p, bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(sent.record(stream));
     return VIL_OK;
-}
-void FrameStage::release() {
-    if (h) hipHostFree(h); if (d) hipFree(d); if (ev) hipEventDestroy(ev);
-    h = nullptr; d = nullptr; cap = 0; ev = nullptr; pending = false;
 }
 
 // ---- LiDAR frame slabs --------------------------------------------------------------------------------------------------------------
@@ -136,7 +129,7 @@ void LidarSlabs::chunks(bool plane, int K, std::vector<int>& out) const {
         for (int s0 = 0; s0 < m; s0 += VIL_THREADS) { out.push_back(slabs[i].slot * cap + s0); out.push_back(std::min(VIL_THREADS, m - s0)); out.push_back(K - ns + i); }
     }
 }
-void LidarSlabs::tables(DevP& P) const { P.pl_c = d_pl; P.pl_stride = nslot * cap_p; P.ed_c = d_ed; P.ed_stride = nslot * cap_e; }
+void LidarSlabs::tables(DevP& P) const { P.pl_c = d_pl.p; P.pl_stride = nslot * cap_p; P.ed_c = d_ed.p; P.ed_stride = nslot * cap_e; }
 void LidarSlabs::reset() {
     slabs.clear(); free_slots.clear();
     for (int q = nslot - 1; q >= 0; --q) free_slots.push_back(q);
@@ -157,18 +150,15 @@ int LidarSlabs::push(hipStream_t stream, int rank, int world, int n_plane, const
     if (n_plane > cap_p || n_edge > cap_e || free_slots.empty()) {
         const int cp2 = std::max(256, std::max(cap_p, ((n_plane + n_plane / 4 + 255) / 256) * 256)), ce2 = std::max(256, std::max(cap_e, ((n_edge + n_edge / 4 + 255) / 256) * 256));
         const int nns = std::max(nslot, count() + 4);
-        double *npl = nullptr, *ned = nullptr;           // both new tables before either old one goes
-        hipError_t e = hipMalloc(&npl, 8 * (size_t)7 * nns * cp2);
-        if (e == hipSuccess) e = hipMalloc(&ned, 8 * (size_t)9 * nns * ce2);
-        if (e != hipSuccess) { if (npl) hipFree(npl); HIPCHK(e); }
+        vilhost::Grown<double> npl, ned;                 // both new tables before either old one goes
+        HIPCHK(npl.reserve((size_t)7 * nns * cp2, (size_t)7 * nns * cp2)); HIPCHK(ned.reserve((size_t)9 * nns * ce2, (size_t)9 * nns * ce2));
         HIPCHK(hipStreamSynchronize(stream));
         for (auto& sl : slabs) {
-            for (int q = 0; q < 7 && sl.np; ++q) HIPCHK(hipMemcpyAsync(npl + ((size_t)q * nns + sl.slot) * cp2, d_pl + ((size_t)q * nslot + sl.slot) * cap_p, 8 * (size_t)sl.np, hipMemcpyDeviceToDevice, stream));
-            for (int q = 0; q < 9 && sl.ne; ++q) HIPCHK(hipMemcpyAsync(ned + ((size_t)q * nns + sl.slot) * ce2, d_ed + ((size_t)q * nslot + sl.slot) * cap_e, 8 * (size_t)sl.ne, hipMemcpyDeviceToDevice, stream));
+            for (int q = 0; q < 7 && sl.np; ++q) HIPCHK(hipMemcpyAsync(npl.p + ((size_t)q * nns + sl.slot) * cp2, d_pl.p + ((size_t)q * nslot + sl.slot) * cap_p, 8 * (size_t)sl.np, hipMemcpyDeviceToDevice, stream));
+            for (int q = 0; q < 9 && sl.ne; ++q) HIPCHK(hipMemcpyAsync(ned.p + ((size_t)q * nns + sl.slot) * ce2, d_ed.p + ((size_t)q * nslot + sl.slot) * cap_e, 8 * (size_t)sl.ne, hipMemcpyDeviceToDevice, stream));
         }
         HIPCHK(hipStreamSynchronize(stream));
-        if (d_pl) hipFree(d_pl); if (d_ed) hipFree(d_ed);
-        d_pl = npl; d_ed = ned;
+        d_pl = std::move(npl); d_ed = std::move(ned);    // (the old tables go with the temporaries, at the end of this block)
         for (int q = nns - 1; q >= nslot; --q) free_slots.push_back(q);
         cap_p = cp2; cap_e = ce2; nslot = nns;
         *tables_moved = true;
@@ -177,33 +167,22 @@ int LidarSlabs::push(hipStream_t stream, int rank, int world, int n_plane, const
     { const int st = stage.begin(stream, 8 * need, 8 * (need + need / 4 + 1024)); if (st != VIL_OK) return st; }
     const int slot = free_slots.back(); free_slots.pop_back();
     if (need) {
-        double* hs = (double*)stage.h; const double* ds = (const double*)stage.d;
+        double* hs = (double*)stage.h.p; const double* ds = (const double*)stage.d.p;
         if (n_plane) memcpy(hs, plane, 8 * (size_t)7 * n_plane);
         if (n_edge) memcpy(hs + (size_t)7 * n_plane, edge, 8 * (size_t)9 * n_edge);
         { const int st = stage.send(stream, 8 * need); if (st != VIL_OK) return st; }
         // point-major rows -> the component-major tables the sweep reads (coalesced, thread = point)
-        if (n_plane) hipLaunchKernelGGL(k_aos2soa, dim3((n_plane + 255) / 256), dim3(256), 0, stream, ds, n_plane, 7, d_pl + (size_t)slot * cap_p, (size_t)nslot * cap_p);
-        if (n_edge) hipLaunchKernelGGL(k_aos2soa, dim3((n_edge + 255) / 256), dim3(256), 0, stream, ds + (size_t)7 * n_plane, n_edge, 9, d_ed + (size_t)slot * cap_e, (size_t)nslot * cap_e);
+        if (n_plane) hipLaunchKernelGGL(k_aos2soa, dim3((n_plane + 255) / 256), dim3(256), 0, stream, ds, n_plane, 7, d_pl.p + (size_t)slot * cap_p, (size_t)nslot * cap_p);
+        if (n_edge) hipLaunchKernelGGL(k_aos2soa, dim3((n_edge + 255) / 256), dim3(256), 0, stream, ds + (size_t)7 * n_plane, n_edge, 9, d_ed.p + (size_t)slot * cap_e, (size_t)nslot * cap_e);
     }
     slabs.push_back({n_plane, n_edge, slot, np_all, ne_all});
     return VIL_OK;
 }
-void LidarSlabs::release() {
-    if (d_pl) hipFree(d_pl); if (d_ed) hipFree(d_ed);
-    d_pl = nullptr; d_ed = nullptr; cap_p = cap_e = nslot = 0;
-    slabs.clear(); free_slots.clear();
-    stage.release();
-}
 
 // ---- the fully resident window ------------------------------------------------------------------------------------------------------
 void Window::release_tables() {
-    hipFree(d_store); hipFree(d_samp); hipFree(d_hdr); hipFree(d_rec); hipFree(d_U); hipFree(d_prior[0]); hipFree(d_prior[1]);
-    d_store = d_samp = d_hdr = d_rec = d_U = d_prior[0] = d_prior[1] = nullptr; is_open = false;
-}
-void Window::release() {
-    release_tables();
-    hipFree(d_wstat); d_wstat = nullptr;
-    stage.release();
+    for (vilhost::Grown<double>* t : {&d_store, &d_samp, &d_hdr, &d_rec, &d_U, &d_prior[0], &d_prior[1]}) t->release();
+    is_open = false;
 }
 int Window::open(hipStream_t stream, const vil_win_cfg* cf) {
     HIPCHK(hipStreamSynchronize(stream));
@@ -213,15 +192,16 @@ int Window::open(hipStream_t stream, const vil_win_cfg* cf) {
         int nblk_max;
         K = cf->K; T = cf->max_tracks; S = cf->max_samples; NF = nf;
         vil_prior_capacity(K, &nmax, &nblk_max, &x0max);
-        HIPCHK(hipMalloc(&d_store, 8 * (size_t)NF * T * VIL_WIN_OBS));
-        HIPCHK(hipMalloc(&d_samp, 8 * (size_t)NF * 7 * S)); HIPCHK(hipMalloc(&d_hdr, 8 * (size_t)NF * 12));
-        HIPCHK(hipMalloc(&d_rec, 8 * (size_t)NF * 287)); HIPCHK(hipMalloc(&d_U, 8 * (size_t)NF * 225));
-        for (int q = 0; q < 2; ++q) HIPCHK(hipMalloc(&d_prior[q], 8 * prior_doubles()));
-        if (!d_wstat) HIPCHK(hipMalloc(&d_wstat, 64));
+        const auto table = [](vilhost::Grown<double>& t, size_t n) { return t.reserve(n, n); };      // (released above: allocates exactly n doubles)
+        HIPCHK(table(d_store, (size_t)NF * T * VIL_WIN_OBS));
+        HIPCHK(table(d_samp, (size_t)NF * 7 * S)); HIPCHK(table(d_hdr, (size_t)NF * 12));
+        HIPCHK(table(d_rec, (size_t)NF * 287)); HIPCHK(table(d_U, (size_t)NF * 225));
+        for (int q = 0; q < 2; ++q) HIPCHK(table(d_prior[q], prior_doubles()));
+        HIPCHK(d_wstat.reserve(16, 16));                 // (kept across dimensions)
     }
-    HIPCHK(hipMemsetAsync(d_store, 0, 8 * (size_t)NF * T * VIL_WIN_OBS, stream));
-    HIPCHK(hipMemsetAsync(d_rec, 0, 8 * (size_t)NF * 287, stream)); HIPCHK(hipMemsetAsync(d_U, 0, 8 * (size_t)NF * 225, stream));
-    HIPCHK(hipMemsetAsync(d_wstat, 0, 64, stream));
+    HIPCHK(hipMemsetAsync(d_store.p, 0, 8 * (size_t)NF * T * VIL_WIN_OBS, stream));
+    HIPCHK(hipMemsetAsync(d_rec.p, 0, 8 * (size_t)NF * 287, stream)); HIPCHK(hipMemsetAsync(d_U.p, 0, 8 * (size_t)NF * 225, stream));
+    HIPCHK(hipMemsetAsync(d_wstat.p, 0, 64, stream));
     cfg = *cf; is_open = true;
     fslot.clear(); islot.clear(); free_f.clear(); free_i.clear();
     for (int q = NF - 1; q >= 0; --q) { free_f.push_back(q); free_i.push_back(q); }
@@ -234,22 +214,22 @@ int Window::push_frame(hipStream_t stream, const vil_win_frame* f) {
     // one staging block, one DMA: [hdr 12 | dt | acc | gyr | observations | track slots]
     const size_t o_samp = 0, o_obs = 8 * (size_t)(12 + 7 * n), o_trk = o_obs + 8 * (size_t)no * VIL_WIN_OBS, total = o_trk + 4 * (size_t)no + 64;
     { const int st = stage.begin(stream, total, 2 * total + 4096); if (st != VIL_OK) return st; }
-    double* hs = (double*)(stage.h + o_samp);
+    double* hs = (double*)(stage.h.p + o_samp);
     memcpy(hs, f->acc0, 24); memcpy(hs + 3, f->gyr0, 24); memcpy(hs + 6, f->lin_ba, 24); memcpy(hs + 9, f->lin_bg, 24);
     double sum = 0.0;
     if (n) { memcpy(hs + 12, f->dt, 8 * (size_t)n); memcpy(hs + 12 + n, f->acc, 24 * (size_t)n); memcpy(hs + 12 + 4 * (size_t)n, f->gyr, 24 * (size_t)n); for (int q = 0; q < n; ++q) sum += f->dt[q]; }
-    if (no) { memcpy(stage.h + o_obs, f->obs, 8 * (size_t)no * VIL_WIN_OBS); memcpy(stage.h + o_trk, f->obs_track, 4 * (size_t)no); }
+    if (no) { memcpy(stage.h.p + o_obs, f->obs, 8 * (size_t)no * VIL_WIN_OBS); memcpy(stage.h.p + o_trk, f->obs_track, 4 * (size_t)no); }
     { const int st = stage.send(stream, o_trk + 4 * (size_t)no); if (st != VIL_OK) return st; }
     const int fs = free_f.back(), is = free_i.back();
     free_f.pop_back(); free_i.pop_back();
     WinFrameIn A;
-    A.n_obs = no; A.track = (const int*)(stage.d + o_trk); A.obs = (const double*)(stage.d + o_obs); A.store = d_store; A.T = T; A.fslot = fs;
-    A.ns = n; A.samp = (const double*)(stage.d + o_samp); A.hdr = d_hdr + 12 * (size_t)is; A.dt = dt(is); A.acc = acc(is); A.gyr = gyr(is);
+    A.n_obs = no; A.track = (const int*)(stage.d.p + o_trk); A.obs = (const double*)(stage.d.p + o_obs); A.store = d_store.p; A.T = T; A.fslot = fs;
+    A.ns = n; A.samp = (const double*)(stage.d.p + o_samp); A.hdr = d_hdr.p + 12 * (size_t)is; A.dt = dt(is); A.acc = acc(is); A.gyr = gyr(is);
     const int nbo = (no * VIL_WIN_OBS + 255) / 256;
     hipLaunchKernelGGL(k_win_frame_in, dim3(nbo + 1), dim3(256), 0, stream, A, nbo);
     if (n > 0) {                                         // the interval's record and its sqrt-information, where the solver will read them
-        vpre_launch_slot(stream, n, dt(is), acc(is), gyr(is), d_hdr + 12 * (size_t)is, cfg.noise, d_rec + 287 * (size_t)is);
-        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, stream, d_rec + 287 * (size_t)is, d_U + 225 * (size_t)is, d_wstat, 1);
+        vpre_launch_slot(stream, n, dt(is), acc(is), gyr(is), d_hdr.p + 12 * (size_t)is, cfg.noise, d_rec.p + 287 * (size_t)is);
+        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, stream, d_rec.p + 287 * (size_t)is, d_U.p + 225 * (size_t)is, d_wstat.p, 1);
     }
     fslot.push_back(fs); islot.push_back(is); ns[is] = n; sum_dt[is] = sum;
     return VIL_OK;
@@ -274,8 +254,8 @@ int Window::drop_frame(hipStream_t stream, int flag, int* lidar_slab) {
     if (ns[ib] > 0) {
         hipLaunchKernelGGL(k_win_append, dim3(1), dim3(256), 0, stream, dt(ia), acc(ia), gyr(ia), ns[ia], dt(ib), acc(ib), gyr(ib), ns[ib]);
         ns[ia] += ns[ib]; sum_dt[ia] += sum_dt[ib];
-        vpre_launch_slot(stream, ns[ia], dt(ia), acc(ia), gyr(ia), d_hdr + 12 * (size_t)ia, cfg.noise, d_rec + 287 * (size_t)ia);
-        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, stream, d_rec + 287 * (size_t)ia, d_U + 225 * (size_t)ia, d_wstat, 1);
+        vpre_launch_slot(stream, ns[ia], dt(ia), acc(ia), gyr(ia), d_hdr.p + 12 * (size_t)ia, cfg.noise, d_rec.p + 287 * (size_t)ia);
+        hipLaunchKernelGGL(k_imu_sqrtinfo, dim3(1), dim3(VIL_THREADS), 0, stream, d_rec.p + 287 * (size_t)ia, d_U.p + 225 * (size_t)ia, d_wstat.p, 1);
     }
     free_f.push_back(fslot[n - 2]); free_i.push_back(ib);
     fslot.erase(fslot.begin() + (n - 2));                // the newest frame's observations and LiDAR points stay where they are
@@ -284,7 +264,7 @@ int Window::drop_frame(hipStream_t stream, int flag, int* lidar_slab) {
     return VIL_OK;
 }
 void Window::fill(WinSlots& ws) const {
-    ws.T = T; ws.store = d_store; ws.fslot = fslot.data(); ws.islot = islot.data(); ws.d_rec = d_rec; ws.d_U = d_U; ws.sum_dt = sum_dt.data();
+    ws.T = T; ws.store = d_store.p; ws.fslot = fslot.data(); ws.islot = islot.data(); ws.d_rec = d_rec.p; ws.d_U = d_U.p; ws.sum_dt = sum_dt.data();
     ws.pJ0 = pJ0(cur); ws.pr0 = pr0(cur); ws.px0 = px0(cur); ws.pH = pH(cur); ws.pg0 = pg0(cur); ws.pc0 = pc0(cur);
 }
 void Window::prior_blocks(vil_prior& p) const {
@@ -296,7 +276,7 @@ int Window::commit_prior(hipStream_t stream, int K_, bool old_, int n, int m, in
     PriorCommit pc; memset(&pc, 0, sizeof pc);
     pc.n = n; pc.nblk = col ? 0 : nblk; pc.J0 = J0; pc.r0 = r0; pc.x = x; pc.K = K_;      // nblk = 0: x0 already in place
     for (int b = 0; b < pc.nblk; ++b) { pc.kind[b] = kind[b]; pc.index[b] = index[b]; }
-    pc.pJ0 = pJ0(dst); pc.pr0 = pr0(dst); pc.px0 = px0(dst); pc.pH = pH(dst); pc.pg0 = pg0(dst); pc.pc0 = pc0(dst); pc.status = d_wstat;
+    pc.pJ0 = pJ0(dst); pc.pr0 = pr0(dst); pc.px0 = px0(dst); pc.pH = pH(dst); pc.pg0 = pg0(dst); pc.pc0 = pc0(dst); pc.status = d_wstat.p;
     const size_t pl = 8 * ((size_t)n * (n + 1) + n + 8);
     if (pl > 48 * 1024 && (int)pl > lds_commit) {        // (hipFuncSetAttribute is not free: raised only when it needs more than it was granted before)
         HIPCHK(hipFuncSetAttribute((const void*)k_prior_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl));
@@ -314,7 +294,7 @@ int Window::commit_prior(hipStream_t stream, int K_, bool old_, int n, int m, in
 }
 int Window::prior_download(hipStream_t stream, vil_prior_out* out, int* h_word) {
     int& wst = *h_word; wst = 0;
-    HIPCHK(hipMemcpyAsync(&wst, d_wstat, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&wst, d_wstat.p, 4, hipMemcpyDeviceToHost, stream));
     out->n = pn; out->nblk = (int)pkind.size(); out->m = pm;
     if (pn > 0) {
         const size_t n = (size_t)pn;
