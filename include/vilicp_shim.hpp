@@ -2,7 +2,7 @@
 // (estimator.cpp:322-421), on plain arrays: the constraint mode and, for the two modes optimization() consumes (:1354, :1376), the
 // relative transform and the square-root information of the ICP factor.  The score itself is vloop_score (villoop.h) at the
 // alignment's result.  Stateless part only: the first_zv bookkeeping over the LidarICPConstraints deque (:392-410, :423-428) and the
-// time stamps (:378-383) stay in the estimator.  Host logic only; nothing here is on the measured path.
+// time stamps (:378-383) are IcpConstraintQueue of vilfront_shim.hpp.  Host logic only; nothing here is on the measured path.
 #ifndef VILICP_SHIM_HPP
 #define VILICP_SHIM_HPP
 

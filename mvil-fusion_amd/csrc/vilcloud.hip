@@ -39,6 +39,7 @@
 
 #include "../../include/vilcloud.h"
 #include "vil_host.hpp"
+#include "vilcloud_stage.hpp"
 #include "vildepth_stage.hpp"
 
 #define VC_BLK 256
@@ -340,6 +341,19 @@ int read_points(vcloud_ctx* c, const size_t offset, const int n_have, float* out
 }
 
 }  // namespace
+
+bool vilcloud_stage::accepts(float leaf, int32_t hist_size) { return finite_positive(leaf) && log2_of_hist(hist_size) >= 0; }
+
+int vilcloud_stage::filter_resident(vcloud_ctx* c, const float4* in, const int* d_n, int n_upper, float leaf, int32_t hist_size, float4* out, int* d_n_out, hipEvent_t ready,
+                                    vilhost::Fence& done) {
+    if (!c || !in || !d_n || !out || !d_n_out || !ready || n_upper < 0 || (size_t)n_upper > c->ntot || !accepts(leaf, hist_size)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
+    VILCHK(hipStreamWaitEvent(c->stream, ready, 0));
+    const int st = enqueue_filter(c, in, d_n, n_upper, leaf, hist_size, out, d_n_out);
+    if (st != VIL_OK) return st;
+    VILCHK(done.record(c->stream));
+    return VIL_OK;
+}
 
 extern "C" {
 

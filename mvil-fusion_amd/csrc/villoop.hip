@@ -23,6 +23,7 @@
 #include "../../include/villoop.h"
 #include "vil_host.hpp"
 #include "vil_knn.hpp"
+#include "villoop_stage.hpp"
 
 #define VL_QPB 4                     // queries (waves) per workgroup of k_loop_grid
 #define VL_BLK VLOOP_SUM_BLOCK
@@ -127,10 +128,11 @@ struct vloop_ctx : vilhost::Device {         // d_mem: target | source | transfo
 
 namespace {
 
-int upload_cloud(vloop_ctx* c, int32_t n, const float* xyz, size_t off) {
+// n points at src (host memory, staged through the pinned buffer, or complete device memory) to the arena at off, and the wait for the copy
+int upload_cloud(vloop_ctx* c, int32_t n, const float* src, size_t off, hipMemcpyKind kind) {
     VILCHK(hipSetDevice(c->device));
-    memcpy(c->h_in, xyz, 12 * (size_t)n);
-    VILCHK(hipMemcpyAsync(c->d_mem + off, c->h_in, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (kind == hipMemcpyHostToDevice) { memcpy(c->h_in, src, 12 * (size_t)n); src = c->h_in; }
+    VILCHK(hipMemcpyAsync(c->d_mem + off, src, 12 * (size_t)n, kind, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));                 // the pinned buffer is free again
     return VIL_OK;
 }
@@ -138,6 +140,21 @@ int upload_cloud(vloop_ctx* c, int32_t n, const float* xyz, size_t off) {
 int build_grid(vloop_ctx* c) {
     VILCHK(vknn::grid_build(c->gb, c->n_tgt, (const float*)(c->d_mem + c->o_tgt), 3, c->grid_h, c->stream));
     c->grid_valid = true;
+    return VIL_OK;
+}
+
+// n points at src become the target: the old search structure dies with the old cloud, the new one is built when the cloud is large enough
+int replace_target(vloop_ctx* c, int32_t n, const float* src, hipMemcpyKind kind) {
+    c->grid_valid = false; c->n_tgt = 0;
+    const int st = upload_cloud(c, n, src, c->o_tgt, kind);
+    if (st != VIL_OK) return st;
+    c->n_tgt = n;
+    if (n >= c->grid_min) {
+        const int sg = build_grid(c);
+        if (sg != VIL_OK) return sg;
+        VILCHK(hipStreamSynchronize(c->stream));
+        VILCHK(hipGetLastError());
+    }
     return VIL_OK;
 }
 
@@ -156,6 +173,20 @@ void inverse_isometry(const double* T, double* D) {
 }
 
 }  // namespace
+
+int villoop_stage::install_source(vloop_ctx* c, int32_t n, const float* src, hipMemcpyKind kind) {
+    if (!c || n < 1 || n > c->max_points || !src) return VIL_ERR_INVALID_ARGUMENT;
+    c->n_src = 0;
+    const int st = upload_cloud(c, n, src, c->o_src, kind);
+    if (st != VIL_OK) return st;
+    c->n_src = n;
+    return VIL_OK;
+}
+
+int villoop_stage::promote_source(vloop_ctx* c) {
+    if (!c || !c->n_src) return VIL_ERR_INVALID_ARGUMENT;
+    return replace_target(c, c->n_src, (const float*)(c->d_mem + c->o_src), hipMemcpyDeviceToDevice);      // the source's copy was waited for
+}
 
 extern "C" {
 
@@ -214,27 +245,13 @@ int vloop_set_grid(vloop_ctx* c, int32_t min_points, double cell) {
 int vloop_set_target(vloop_ctx* c, int32_t n, const float* xyz) {
     if (!c || n < 1 || n > c->max_points || !xyz) return VIL_ERR_INVALID_ARGUMENT;
     if (!all_finite(xyz, 3 * (size_t)n)) return VIL_ERR_NON_FINITE;
-    c->grid_valid = false; c->n_tgt = 0;                     // the old search structure dies with the old cloud
-    const int st = upload_cloud(c, n, xyz, c->o_tgt);
-    if (st != VIL_OK) return st;
-    c->n_tgt = n;
-    if (n >= c->grid_min) {
-        const int sg = build_grid(c);
-        if (sg != VIL_OK) return sg;
-        VILCHK(hipStreamSynchronize(c->stream));
-        VILCHK(hipGetLastError());
-    }
-    return VIL_OK;
+    return replace_target(c, n, xyz, hipMemcpyHostToDevice);
 }
 
 int vloop_set_source(vloop_ctx* c, int32_t n, const float* xyz) {
     if (!c || n < 1 || n > c->max_points || !xyz) return VIL_ERR_INVALID_ARGUMENT;
     if (!all_finite(xyz, 3 * (size_t)n)) return VIL_ERR_NON_FINITE;
-    c->n_src = 0;
-    const int st = upload_cloud(c, n, xyz, c->o_src);
-    if (st != VIL_OK) return st;
-    c->n_src = n;
-    return VIL_OK;
+    return villoop_stage::install_source(c, n, xyz, hipMemcpyHostToDevice);
 }
 
 int vloop_score(vloop_ctx* c, int32_t n_T, const double* T16s, double max_range, double* scores, int32_t* n_used, float* nn_d2, int32_t* nn_idx) {

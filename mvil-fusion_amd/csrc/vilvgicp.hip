@@ -28,6 +28,7 @@
 #include "vil_knn.hpp"
 #include "vil_math.hpp"
 #include "vil_tuning.hpp"
+#include "vilvgicp_stage.hpp"
 
 #define VG_THREADS 256
 #define VGA_THREADS 512     // k_vgicp_align: one slot per thread on the usual scan (a pass is a chain of dependent gathers per slot; two waves per SIMD hide part of it)
@@ -379,6 +380,21 @@ static hipError_t sum_and_fetch(vgicp_ctx* c, int nblk) {
     return hipStreamSynchronize(c->stream);
 }
 
+bool vilvgicp_stage::accepts(const vgicp_options& o) { return o.neighbor_mode == VGICP_DIRECT1 || o.neighbor_mode == VGICP_DIRECT7 || o.neighbor_mode == VGICP_DIRECT27; }
+
+int vilvgicp_stage::install_source(vgicp_ctx* c, int32_t n, const float* src, const double* cov9, hipMemcpyKind kind) {
+    if (!c || n <= 0 || !src || (cov9 && kind != hipMemcpyHostToDevice)) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
+    c->n = 0;                                              // no source until this one is complete
+    VILCHK(c->d_sxyz.reserve(3 * (size_t)n, 3 * (size_t)n)); VILCHK(c->d_scov.reserve(9 * (size_t)n, 9 * (size_t)n));
+    if (kind == hipMemcpyHostToDevice) VILCHK(hipMemcpy(c->d_sxyz.p, src, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
+    else VILCHK(hipMemcpyAsync(c->d_sxyz.p, src, 4 * 3 * (size_t)n, kind, c->stream));       // in order before the estimate, whose wait ends it
+    if (cov9) VILCHK(hipMemcpy(c->d_scov.p, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
+    else { const int st = covariances_dev(c, n, c->d_sxyz.p, KNN_MAX, c->d_scov.p); if (st != VIL_OK) return st; }      // source covariances never leave the device
+    c->n = n; c->linearized = false;
+    return VIL_OK;
+}
+
 extern "C" {
 
 int vgicp_covariances(vgicp_ctx* c, int32_t n, const float* xyz, int32_t k, double* out) {
@@ -509,15 +525,7 @@ int vgicp_build_profile_read(vgicp_ctx* c, int64_t* launches, double* total_ms) 
 }
 
 int vgicp_set_source(vgicp_ctx* c, int32_t n, const float* xyz, const double* cov9) {
-    if (!c || n <= 0 || !xyz) return VIL_ERR_INVALID_ARGUMENT;
-    VILCHK(hipSetDevice(c->device));
-    c->n = 0;                                              // no source until this one is complete
-    VILCHK(c->d_sxyz.reserve(3 * (size_t)n, 3 * (size_t)n)); VILCHK(c->d_scov.reserve(9 * (size_t)n, 9 * (size_t)n));
-    VILCHK(hipMemcpy(c->d_sxyz.p, xyz, 4 * 3 * (size_t)n, hipMemcpyHostToDevice));
-    if (cov9) VILCHK(hipMemcpy(c->d_scov.p, cov9, 8 * 9 * (size_t)n, hipMemcpyHostToDevice));
-    else { const int st = covariances_dev(c, n, c->d_sxyz.p, KNN_MAX, c->d_scov.p); if (st != VIL_OK) return st; }      // source covariances never leave the device
-    c->n = n; c->linearized = false;
-    return VIL_OK;
+    return vilvgicp_stage::install_source(c, n, xyz, cov9, hipMemcpyHostToDevice);
 }
 
 int vgicp_linearize(vgicp_ctx* c, const double* T, int32_t mode, double* err, double* H, double* b, int32_t* n_corr) {
@@ -862,7 +870,7 @@ int vgicp_set_knn_grid(vgicp_ctx* c, int32_t min_points, double cell) {
 
 int vgicp_align(vgicp_ctx* c, const double* guess, const vgicp_options* o, double* T_out, vgicp_summary* out) {
     if (!c || !guess || !o || !T_out || !out) return VIL_ERR_INVALID_ARGUMENT;
-    if (!c->live.nvox || !c->n || (o->neighbor_mode != VGICP_DIRECT1 && o->neighbor_mode != VGICP_DIRECT7 && o->neighbor_mode != VGICP_DIRECT27)) return VIL_ERR_INVALID_ARGUMENT;
+    if (!c->live.nvox || !c->n || !vilvgicp_stage::accepts(*o)) return VIL_ERR_INVALID_ARGUMENT;
     if (VIL_TUNE_ENV("VGICP_HOST_LOOP")) return vgicp_align_host(c, guess, o, T_out, out);       // the step logic on the host between launches (cross-check)
     VILCHK(hipSetDevice(c->device));
     const int mode = o->neighbor_mode, slots = c->n * mode, nblk = (slots + VGA_THREADS - 1) / VGA_THREADS;
