@@ -1,4 +1,4 @@
-"""The ctypes handle the row wrappers share (scanreg, depthreg, scancontext, loopverify, mapreg, vgicp, preint, track, epipolar, clahe, feat, cloud, lidarfront): one context behind one C prefix,
+"""The ctypes handle the row wrappers share (scanreg, depthreg, scancontext, loopverify, mapreg, vgicp, preint, track, epipolar, clahe, feat, cloud, lidarfront, localmap): one context behind one C prefix,
 a status check on every call, close / __del__, and the kernel profiler of the rows that have one."""
 import ctypes as C
 

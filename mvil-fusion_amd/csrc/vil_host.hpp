@@ -1,5 +1,5 @@
 // vil_host.hpp -- the host scaffold shared by the row libraries (vilmap.hip, vilvgicp.hip, vilpreint.hip, vilscan.hip, vildepth.hip,
-// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip, vilfront.hip; through vil_voxmap.hpp and vil_knn.hpp
+// vilsc.hip, villoop.hip, vilpgo.hip, vilgmap.hip, viltrack.hip, vilepi.hip, vilclahe.hip, vilfeat.hip, vilcloud.hip, vilfront.hip, villmap.hip; through vil_voxmap.hpp and vil_knn.hpp
 // also their headers) and, through vil_comm.hpp and vil_resident.hpp, by the solver itself (vilsolve.hip, vilwindow.hip, vilcomm.hip): one check macro, the
 // arena layout, the owner of a row's stream / arena / pinned buffers, the kernel-event profilers, the grow-only buffer (Grown), the mapped pinned record
 // (Mapped), the poll of a word in it (await_word) and the event behind a staging copy (Fence).  Everything the solver's context allocates is one of these.

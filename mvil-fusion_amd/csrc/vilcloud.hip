@@ -39,6 +39,7 @@
 
 #include "../../include/vilcloud.h"
 #include "vil_host.hpp"
+#include "vilcloud_dev.hpp"
 #include "vilcloud_stage.hpp"
 #include "vildepth_stage.hpp"
 
@@ -56,8 +57,8 @@ static_assert(K_FUSE + 1 == VCLOUD_NUM_KERNELS, "one profile entry per kernel");
 // the device header (ints): the point counts of one push, of one vcloud_filter, and the three counts filter A keeps for itself
 enum { H_RAW = 0, H_DS, H_VIEW, H_FUSED, H_CLOUD, H_FIN, H_FOUT, H_VALID, H_EVICT, H_NONEMPTY, H_INTS = 16 };
 
-__device__ __forceinline__ bool same_voxel(const int4 a, const int4 b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
-__device__ __forceinline__ bool fits_int(const float f) { return f >= -2147483648.0f && f < 2147483648.0f; }      // false for NaN
+// the voxel, the ranking by ballots, the eviction flag and the run's sum are shared with villmap.hip's one-workgroup-per-cube filter
+using namespace vilcloud_dev;
 
 // steps 1-2: vox[i] = (ix, iy, iz, bucket), bucket -1 for a dropped point and for i >= n; the eviction flags are cleared
 __global__ __launch_bounds__(VC_BLK) void k_cloud_keys(const int* __restrict__ d_n, int n_upper, const float4* __restrict__ in, float inv, unsigned hmask,
@@ -65,45 +66,18 @@ __global__ __launch_bounds__(VC_BLK) void k_cloud_keys(const int* __restrict__ d
     const int i = blockIdx.x * VC_BLK + threadIdx.x;
     if (i >= n_upper) return;
     evict[i] = 0;
-    int4 v = make_int4(0, 0, 0, -1);
-    if (i < *d_n) {
-        const float4 p = in[i];
-        const float fx = floorf(p.x * inv), fy = floorf(p.y * inv), fz = floorf(p.z * inv);
-        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && fits_int(fx) && fits_int(fy) && fits_int(fz)) {
-            const int ix = (int)fx, iy = (int)fy, iz = (int)fz;
-            const unsigned h = ((unsigned)ix * 7171u + (unsigned)iy * 3079u + (unsigned)iz * 4231u) & hmask;
-            v = make_int4(ix, iy, iz, (int)h);
-        }
-    }
-    vox[i] = v;
+    vox[i] = i < *d_n ? voxel_of(in[i], inv, hmask) : make_int4(0, 0, 0, -1);
 }
 
-// The ranking both sort passes share.  hist: the wave's H counters.  SCATTER = false: they start at 0 and end as the segment's histogram;
-// SCATTER = true: they start at the segment's offsets and every point's index goes to its place.  All four waves of a workgroup take the
-// same number of steps, so the barriers are uniform; a wave only ever touches its own counters.
+// The ranking both sort passes share (rank_piece of vilcloud_dev.hpp) for a wave's segment.  hist: the wave's H counters.  SCATTER = false:
+// they start at 0 and end as the segment's histogram; SCATTER = true: they start at the segment's offsets.
 template <bool SCATTER>
 __device__ __forceinline__ void rank_segment(const int n, const int4* __restrict__ vox, const int H, const int bits, const int nseg, int* __restrict__ table,
                                              int* __restrict__ sorted, int* hist) {
     const int lane = threadIdx.x & 63, seg = blockIdx.x * VC_WAVES + (threadIdx.x >> 6);
     for (int b = lane; b < H; b += 64) hist[b] = SCATTER ? table[(size_t)b * nseg + seg] : 0;
     __syncthreads();
-    for (int step = 0; step < VC_WAVE_PTS / 64; ++step) {
-        const int i = seg * VC_WAVE_PTS + step * 64 + lane;
-        const int h = i < n ? vox[i].w : -1;
-        const bool valid = h >= 0;
-        unsigned long long same = __ballot(valid);
-        for (int bit = 0; bit < bits; ++bit) {
-            const bool one = (h >> bit) & 1;
-            const unsigned long long bb = __ballot(one);
-            same &= one ? bb : ~bb;
-        }
-        const int rank = __popcll(same & ((1ull << lane) - 1ull));
-        const int old = valid ? hist[h] : 0;                                                       // h < H: the bucket was masked with H - 1
-        __syncthreads();
-        if (valid && rank == 0) hist[h] = old + __popcll(same);
-        if (SCATTER && valid) sorted[old + rank] = i;                                              // old + rank < points that are not dropped <= n
-        __syncthreads();
-    }
+    rank_piece<SCATTER>(seg * VC_WAVE_PTS, VC_WAVE_PTS / 64, n, vox, bits, sorted, hist);
     if (!SCATTER) for (int b = lane; b < H; b += 64) table[(size_t)b * nseg + seg] = hist[b];
 }
 
@@ -181,9 +155,7 @@ __global__ __launch_bounds__(VC_SCAN) void k_cloud_scan(int* __restrict__ a, int
 __global__ __launch_bounds__(VC_BLK) void k_cloud_runs(const int* __restrict__ hdr, int n_upper, const int4* __restrict__ vox, const int* __restrict__ sorted, int* __restrict__ evict) {
     const int p = blockIdx.x * VC_BLK + threadIdx.x;
     if (p == 0 || p >= min(hdr[H_VALID], n_upper)) return;
-    const int i = sorted[p];                                                                       // sorted holds indices < n of points that were not dropped
-    const int4 v = vox[i], u = vox[sorted[p - 1]];
-    if (u.w == v.w && !same_voxel(u, v)) evict[i] = 1;
+    flag_eviction(p, vox, sorted, evict);
 }
 
 // brank[b]: the non-empty buckets before b.  The bucket's first place is its entry of segment 0 in the offset table.
@@ -210,23 +182,7 @@ __global__ __launch_bounds__(VC_BLK) void k_cloud_emit(const int* hdr, int n_upp
     const int nv = min(hdr[H_VALID], n_upper), n_evict = hdr[H_EVICT];
     if (p == 0) *d_n_out = n_evict + hdr[H_NONEMPTY];
     if (p >= nv) return;
-    const int i = sorted[p];
-    const int4 v = vox[i];
-    if (p > 0 && same_voxel(vox[sorted[p - 1]], v)) return;                                        // not a run start
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
-    int cnt = 0, q = p, j = i;
-    int4 u = v;
-    do {                                                                                           // step 4, in index order
-        const float4 pt = in[j];
-        sx = sx + pt.x; sy = sy + pt.y; sz = sz + pt.z; sw = sw + pt.w;
-        ++cnt; ++q;
-        if (q < nv) { j = sorted[q]; u = vox[j]; }
-    } while (q < nv && same_voxel(u, v));
-    const float c = (float)cnt;
-    // a successor in the bucket: flushed when the successor's first point arrives, position = the evictions before that point; the bucket's
-    // last run: flushed at the end.  evpos[j] < n_evict and n_evict + brank < runs <= n_upper: inside `out`
-    const int pos = (q < nv && u.w == v.w) ? evpos[j] : n_evict + brank[v.w];
-    out[pos] = make_float4(sx / c, sy / c, sz / c, sw / c);
+    emit_run(p, nv, n_evict, in, vox, sorted, evpos, brank, out);
 }
 
 // step 2 of the accumulation

@@ -22,6 +22,7 @@
 #include "vil_coop.hpp"
 #include "vil_knn.hpp"
 #include "vil_pose1.hpp"
+#include "vilmap_stage.hpp"
 
 #define VM_THREADS 256
 
@@ -238,14 +239,14 @@ __global__ __launch_bounds__(VM_THREADS) void k_map_compact(int nqc, int nqs, co
     if (b == (int)gridDim.x - 1 && t < 2) cnt[t] = s_off[t] + blk[2 * b + t];
 }
 
-void quat_to_R(const double* q, double* R) {
+}  // namespace
+
+void vilmap_stage::quat_to_R(const double* q, double* R) {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
     R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
     R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
     R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
 }
-
-}  // namespace
 
 struct __attribute__((visibility("hidden"))) vmap_ctx : vilhost::Device {                  // its buffers grow on demand: no arena; every member frees itself (vil_host.hpp)
     int nc = 0, ns = 0;
@@ -260,6 +261,7 @@ struct __attribute__((visibility("hidden"))) vmap_ctx : vilhost::Device {       
     vilhost::Grown<char> d_reg; vilhost::Grown<char, true> h_reg;      // single-submission registration: pose (7 doubles) | PoseRT | 2 x Pose1Out, and its pinned mirror
     vilhost::Mapped res;                               // the second round's Pose1Out | sequence word, written by k_pose_solve, polled by the host
     int coop_cap = -1;                                 // workgroups of k_pose_solve the device holds at once (vil_coop.hpp)
+    bool rt_valid = false;                             // d_reg holds the PoseRT of the last call's last solve (vilmap_stage::device_pose)
     int fused_max = 1 << 20;                           // scans up to this many points take the one-launch pose solve (vmap_set_fused_max; 0 = always the window solver)
     vilhost::Profiler<2, 4> prof;                      // k_map_search, k_map_fit
 };
@@ -284,11 +286,18 @@ hipError_t reserve_pair(vilhost::Grown<T>& d, vilhost::Grown<T, true>& h, size_t
     return e;
 }
 
-int upload_scan(vmap_ctx* c, int n_corner, const float* corner, int n_surf, const float* surf) {
+// kind: where corner and surf live.  Host pointers (vmap_associate, vmap_align) go through the pinned image, device pointers
+// (vilmap_stage) straight into the staging buffer; either way d_scan holds the corner block, then the surf block.
+int upload_scan(vmap_ctx* c, int n_corner, const float* corner, int n_surf, const float* surf, hipMemcpyKind kind = hipMemcpyHostToDevice) {
     const int nq = n_corner + n_surf;
     const size_t need_scan = 4 * (size_t)nq + 4, need_work = ScanWork::bytes((size_t)nq);      // (floats, bytes)
     VILCHK(c->d_scan.reserve(need_scan, 2 * need_scan));
     VILCHK(c->d_work.reserve(need_work, 2 * need_work));
+    if (kind == hipMemcpyDeviceToDevice) {
+        if (n_corner) VILCHK(hipMemcpyAsync(c->d_scan.p, corner, 16 * (size_t)n_corner, kind, c->stream));
+        if (n_surf) VILCHK(hipMemcpyAsync(c->d_scan.p + 4 * (size_t)n_corner, surf, 16 * (size_t)n_surf, kind, c->stream));
+        return VIL_OK;
+    }
     // through a pinned image: one DMA instead of two staged pageable copies (every entry point ends with a stream
     // synchronisation, so the image is free again when the next call starts)
     VILCHK(c->h_scan.reserve(need_scan, 2 * need_scan));
@@ -324,7 +333,7 @@ int enqueue_association(vmap_ctx* c, int n_corner, int n_surf, const PoseD& T, c
     if (tb) hipLaunchKernelGGL(k_map_compact, per_point, dim3(VM_THREADS), 0, c->stream, n_corner, n_surf, w.slot, w.blk, tb->edge, tb->es, tb->plane, tb->ps, c->d_cnt.p);
     return VIL_OK;
 }
-PoseD pose_of(const double* q, const double* t) { PoseD T; quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2]; return T; }
+PoseD pose_of(const double* q, const double* t) { PoseD T; vilmap_stage::quat_to_R(q, T.R); T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2]; return T; }
 
 // association of the uploaded scan at pose (q, t); compacted on the host in scan order
 int associate_uploaded(vmap_ctx* c, int n_corner, int n_surf, const double* q, const double* t, int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
@@ -417,35 +426,20 @@ int align_fused(vmap_ctx* c, int n_corner, int n_surf, double* q, double* t, con
     if (r[1].status != 0) return r[1].status;
     t[0] = r[1].pose[0]; t[1] = r[1].pose[1]; t[2] = r[1].pose[2]; q[0] = r[1].pose[3]; q[1] = r[1].pose[4]; q[2] = r[1].pose[5]; q[3] = r[1].pose[6];
     out->rounds = 2; out->n_edge = r[1].n_edge; out->n_plane = r[1].n_plane; out->iterations = r[1].iterations; out->initial_cost = r[1].initial_cost; out->final_cost = r[1].final_cost;
+    c->rt_valid = true;                                  // the second solve's PoseRT stays at d_reg + REG_RT until the next call
     out->t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // one submission: association and solve are not separable on the host clock
     return VIL_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int vmap_create(int32_t device, vmap_ctx** out) {
-    if (!out) return VIL_ERR_INVALID_ARGUMENT;
-    vmap_ctx* c = new vmap_ctx();
-    const hipError_t err = c->open(device, 0);
-    if (err != hipSuccess) { delete c; VILCHK(err); }                    // without an arena a failed open() holds nothing
-    *out = c;
-    return VIL_OK;
-}
-void vmap_destroy(vmap_ctx* c) {
-    if (!c) return;
-    c->close(c->prof);
-    delete c;
-}
-
-int vmap_set_map(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const float* surf) {
+// vmap_set_map and vilmap_stage::set_map_resident: kind says where corner and surf live
+int set_map_from(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const float* surf, hipMemcpyKind kind) {
     if (!c || nc < 0 || ns < 0 || (nc && !corner) || (ns && !surf)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
     c->nc = 0; c->ns = 0;
     VILCHK(c->d_cmap.reserve(4 * (size_t)nc, 6 * (size_t)nc));
     VILCHK(c->d_smap.reserve(4 * (size_t)ns, 6 * (size_t)ns));
-    if (nc) VILCHK(hipMemcpyAsync(c->d_cmap.p, corner, 16 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
-    if (ns) VILCHK(hipMemcpyAsync(c->d_smap.p, surf, 16 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
+    if (nc) VILCHK(hipMemcpyAsync(c->d_cmap.p, corner, 16 * (size_t)nc, kind, c->stream));
+    if (ns) VILCHK(hipMemcpyAsync(c->d_smap.p, surf, 16 * (size_t)ns, kind, c->stream));
     if (nc) VILCHK(vknn::grid_build_adaptive(c->gc, nc, c->d_cmap.p, 4, c->hc, VM_OCC, c->stream));
     if (ns) VILCHK(vknn::grid_build_adaptive(c->gs, ns, c->d_smap.p, 4, c->hs, VM_OCC, c->stream));
     VILCHK(hipStreamSynchronize(c->stream));
@@ -453,36 +447,16 @@ int vmap_set_map(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const
     return VIL_OK;
 }
 
-int vmap_associate(vmap_ctx* c, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf, const double* q, const double* t,
-                   int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
-    if (!c || !q || !t || !n_edge || !n_plane || n_corner < 0 || n_surf < 0 || (n_corner && (!corner || !edge9)) || (n_surf && (!surf || !plane7))) return VIL_ERR_INVALID_ARGUMENT;
-    VILCHK(hipSetDevice(c->device));
-    const int st = upload_scan(c, n_corner, corner, n_surf, surf);
-    if (st != VIL_OK) return st;
-    return associate_uploaded(c, n_corner, n_surf, q, t, n_edge, edge9, n_plane, plane7);
-}
-
-int vmap_set_fused_max(vmap_ctx* c, int32_t max_points) { if (!c || max_points < 0) return VIL_ERR_INVALID_ARGUMENT; c->fused_max = max_points; return VIL_OK; }
-
-int vmap_profile_enable(vmap_ctx* c, int32_t enable) {
-    if (!c) return VIL_ERR_INVALID_ARGUMENT;
-    VILCHK(c->prof.enable(c->device, enable != 0));
-    return VIL_OK;
-}
-int vmap_profile_read(vmap_ctx* c, int64_t* launches2, double* total_ms2) {
-    if (!c || !launches2 || !total_ms2) return VIL_ERR_INVALID_ARGUMENT;
-    c->prof.read(launches2, total_ms2);
-    return VIL_OK;
-}
-
-int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf,
-               double* q, double* t, const vil_options* opts, vmap_summary* out) {
+// vmap_align and vilmap_stage::align_resident: kind says where corner and surf live
+int align_from(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf,
+               double* q, double* t, const vil_options* opts, vmap_summary* out, hipMemcpyKind kind) {
     if (!c || !solver || !q || !t || !opts || !out) return VIL_ERR_INVALID_ARGUMENT;
     memset(out, 0, sizeof *out);
+    c->rt_valid = false;
     if (!(c->nc > 10 && c->ns > 50)) return VIL_OK;                      // localMapping.cpp:586 "corner and surf num are not enough"
     if (n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf)) return VIL_ERR_INVALID_ARGUMENT;
     VILCHK(hipSetDevice(c->device));
-    int st = upload_scan(c, n_corner, corner, n_surf, surf);             // the scan is uploaded once for both rounds
+    int st = upload_scan(c, n_corner, corner, n_surf, surf, kind);             // the scan is uploaded once for both rounds
     if (st != VIL_OK) return st;
     if (c->coop_cap < 0) c->coop_cap = vilcoop::capacity((const void*)vp1::k_pose_solve, VP1_THREADS, 0, c->device);
     if (n_corner + n_surf <= c->fused_max && c->coop_cap >= 1) return align_fused(c, n_corner, n_surf, q, t, opts, out);
@@ -510,6 +484,59 @@ int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corn
         out->rounds = round + 1; out->n_edge = ne; out->n_plane = np; out->iterations = sum.iterations; out->initial_cost = sum.initial_cost; out->final_cost = sum.final_cost;
     }
     return VIL_OK;
+}
+}  // namespace
+
+int vilmap_stage::set_map_resident(vmap_ctx* c, int32_t nc, const float* d_corner, int32_t ns, const float* d_surf) { return set_map_from(c, nc, d_corner, ns, d_surf, hipMemcpyDeviceToDevice); }
+int vilmap_stage::align_resident(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* d_corner, int32_t n_surf, const float* d_surf, double* q, double* t, const vil_options* opts,
+                                 vmap_summary* out) {
+    return align_from(c, solver, n_corner, d_corner, n_surf, d_surf, q, t, opts, out, hipMemcpyDeviceToDevice);
+}
+const double* vilmap_stage::device_pose(vmap_ctx* c) { return c && c->rt_valid ? (const double*)(c->d_reg.p + REG_RT) : nullptr; }
+
+extern "C" {
+
+int vmap_create(int32_t device, vmap_ctx** out) {
+    if (!out) return VIL_ERR_INVALID_ARGUMENT;
+    vmap_ctx* c = new vmap_ctx();
+    const hipError_t err = c->open(device, 0);
+    if (err != hipSuccess) { delete c; VILCHK(err); }                    // without an arena a failed open() holds nothing
+    *out = c;
+    return VIL_OK;
+}
+void vmap_destroy(vmap_ctx* c) {
+    if (!c) return;
+    c->close(c->prof);
+    delete c;
+}
+
+int vmap_set_map(vmap_ctx* c, int32_t nc, const float* corner, int32_t ns, const float* surf) { return set_map_from(c, nc, corner, ns, surf, hipMemcpyHostToDevice); }
+
+int vmap_associate(vmap_ctx* c, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf, const double* q, const double* t,
+                   int32_t* n_edge, double* edge9, int32_t* n_plane, double* plane7) {
+    if (!c || !q || !t || !n_edge || !n_plane || n_corner < 0 || n_surf < 0 || (n_corner && (!corner || !edge9)) || (n_surf && (!surf || !plane7))) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(hipSetDevice(c->device));
+    const int st = upload_scan(c, n_corner, corner, n_surf, surf);
+    if (st != VIL_OK) return st;
+    return associate_uploaded(c, n_corner, n_surf, q, t, n_edge, edge9, n_plane, plane7);
+}
+
+int vmap_set_fused_max(vmap_ctx* c, int32_t max_points) { if (!c || max_points < 0) return VIL_ERR_INVALID_ARGUMENT; c->fused_max = max_points; return VIL_OK; }
+
+int vmap_profile_enable(vmap_ctx* c, int32_t enable) {
+    if (!c) return VIL_ERR_INVALID_ARGUMENT;
+    VILCHK(c->prof.enable(c->device, enable != 0));
+    return VIL_OK;
+}
+int vmap_profile_read(vmap_ctx* c, int64_t* launches2, double* total_ms2) {
+    if (!c || !launches2 || !total_ms2) return VIL_ERR_INVALID_ARGUMENT;
+    c->prof.read(launches2, total_ms2);
+    return VIL_OK;
+}
+
+int vmap_align(vmap_ctx* c, vil_ctx* solver, int32_t n_corner, const float* corner, int32_t n_surf, const float* surf,
+               double* q, double* t, const vil_options* opts, vmap_summary* out) {
+    return align_from(c, solver, n_corner, corner, n_surf, surf, q, t, opts, out, hipMemcpyHostToDevice);
 }
 
 }  // extern "C"
